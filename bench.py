@@ -30,7 +30,14 @@ anything touches the GPU) and n_gpus is the job's world size.  Roots are indepen
          147 dependent launches per env step (profiles/round6/strong_proxy.json).
 `--strong` swaps the two.  The barrier / max-over-ranks clock uses torch.distributed (RCCL).
 
-Also reported (rank 0, N=1 only):
+A plain run sets up, warms up, times --steps env steps and prints the line ("roofline" and
+"cpu_baseline" null).  `--dump-outputs DIR` then writes what the last timed step computed, per agent
+search i: DIR/search<i>_<name>.npy (float32) -- the root values and marginal visit counts, and the
+last fused step's selection (idx, idy, act) and gathered hidden states (leaf).  The inputs, the
+hidden-state pool included, are functions of --seed alone, so two builds can be compared output for
+output.
+
+Also reported with `--full` (rank 0; the CPU baseline at N=1 only):
   roofline      dominant kernel = the fused simulation step (49 of 52 launches): algorithmic bytes per
                 launch (SURVEY §8d formula over the kernel's own counters) / its average duration,
                 measured with HIP events on the launch stream around a graph of one search's 49
@@ -80,7 +87,13 @@ def parse(argv=None):
                     help="N > 1: headline value from the strong-scaling leg (--roots roots split over the GPUs) "
                          "instead of the weak one (--roots roots on every GPU)")
     ap.add_argument("--no-graph", action="store_true")
-    ap.add_argument("--no-cpu", action="store_true", help="skip the CPU baseline leg")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: the fused kernel's roofline "
+                         "(a timed run of its own) and the CPU baseline legs; off by default")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed (the search outputs, the "
+                         "last fused step's selection and gathered hidden states) as DIR/<name>.npy, float32")
+    ap.add_argument("--no-cpu", action="store_true", help="with --full: skip the CPU baseline leg")
     ap.add_argument("--cpu-seconds", type=float, default=10.0)
     ap.add_argument("--cpu-procs", type=int, default=16,
                     help="processes of the multi-core CPU baseline (at most this process's CPU share)")
@@ -140,6 +153,9 @@ class HipLeg:
         def dev_t(a):
             return torch.from_numpy(np.ascontiguousarray(a)).to(dev)
 
+        # the hidden-state pools are part of the inputs: the same from run to run (--dump-outputs)
+        gen = torch.Generator(device=dev)
+        gen.manual_seed(args.seed * 1000 + root_offset)
         self.searches = []
         for inp in self.host_inputs:
             tb = Tree_batch(B, 1, A, K, S, d["delta_lb"], inp.seed, d["rho"], d["lam"], root_offset=root_offset,
@@ -154,7 +170,7 @@ class HipLeg:
                 rr=dev_t(inp.root_reward), rv=dev_t(inp.root_value), rp=dev_t(inp.root_policy),
                 rb=dev_t(inp.root_beta), rn=dev_t(inp.root_noise), eps=inp.noise_eps,
                 r=net[:, :B], v=net[:, B:2 * B], p=net[:, 2 * B:2 * B + B * A], b=net[:, 2 * B + B * A:],
-                pool=torch.randn(S + 1, B, self.H, device=dev),
+                pool=torch.randn(S + 1, B, self.H, device=dev, generator=gen),
                 leaf=torch.empty(B, self.H, device=dev),
                 idx=sel[0], idy=sel[1], act=sel[2].view(B, 1),
                 values=torch.empty(B, device=dev),
@@ -212,6 +228,19 @@ class HipLeg:
 
     def stats(self):
         return [sd["tb"].stats() for sd in self.searches]
+
+    def outputs(self):
+        """What the last env step left its caller (--dump-outputs), per agent search: the search
+        outputs, and the last fused step's selection and gathered hidden states."""
+        import torch
+
+        torch.cuda.synchronize()
+        out = {}
+        for i, sd in enumerate(self.searches):
+            for k, name in (("values", "values"), ("visits", "marginal_visit_count"), ("idx", "sel_idx"),
+                            ("idy", "sel_idy"), ("act", "sel_act"), ("leaf", "leaf")):
+                out[f"search{i}_{name}"] = sd[k].cpu().numpy()
+        return out
 
     def run(self, steps, before_step=None):
         import torch
@@ -407,6 +436,7 @@ class DropinLeg:
 
         d, S, K = self.d, self.S, self.K
         c2, c1, g = d["pb_c_base"], d["pb_c_init"], d["discount"]
+        out = []
         for inp in self.host_inputs:
             tb = Tree_batch(self.B, 1, self.A, K, S, d["delta_lb"], inp.seed, d["rho"], d["lam"],
                             root_offset=self.root_offset, lib=self.lib)
@@ -415,8 +445,8 @@ class DropinLeg:
             for s in range(S):
                 tb.batch_selection(c2, c1, g)
                 tb.batch_expansion_and_backup(s + 1, g, K, inp.reward[s], inp.value[s], inp.policy[s], inp.beta[s])
-            tb.get_roots_values()
-            tb.get_roots_marginal_visit_count()
+            out.append((tb.get_roots_values(), tb.get_roots_marginal_visit_count()))
+        self.last = out
 
     def prepare(self):
         for _ in range(max(1, self.args.warmup)):
@@ -424,6 +454,13 @@ class DropinLeg:
 
     def check(self):
         pass
+
+    def outputs(self):
+        out = {}
+        for i, (values, visits) in enumerate(self.last):
+            out[f"search{i}_values"] = np.asarray(values)
+            out[f"search{i}_marginal_visit_count"] = np.asarray(visits)
+        return out
 
     def run(self, steps, before_step=None):
         for i in range(steps):
@@ -467,6 +504,9 @@ class PortLeg:
 
     def check(self):
         pass
+
+    def outputs(self):
+        return {f"search{i}_values": np.asarray(v) for i, v in enumerate(self.values)}
 
     def run(self, steps, before_step=None):
         for i in range(steps):
@@ -581,6 +621,27 @@ def rank_record(rank, local, dev, legs, steps):
     return rec
 
 
+DUMP_LIMIT = 48 << 20  # bytes --dump-outputs writes at most, all files together
+
+
+def dump_outputs(path, arrays, prefix=""):
+    """--dump-outputs: every array as <path>/<prefix><name>.npy, float32 (float64 stays float64).
+    Past DUMP_LIMIT in all, an array over its equal share is written as a fixed, seeded sample of
+    its flattened elements (the same elements in every run)."""
+    os.makedirs(path, exist_ok=True)
+    arrays = {k: np.asarray(v) for k, v in arrays.items()}
+    arrays = {k: v.astype(np.float64 if v.dtype == np.float64 else np.float32) for k, v in arrays.items()}
+    if sum(v.nbytes for v in arrays.values()) > DUMP_LIMIT:
+        share = DUMP_LIMIT // max(1, len(arrays))
+        for j, k in enumerate(sorted(arrays)):
+            v = arrays[k]
+            if v.nbytes > share:
+                pick = np.sort(np.random.default_rng(j).choice(v.size, share // v.itemsize, replace=False))
+                arrays[k] = v.reshape(-1)[pick]
+    for k, v in arrays.items():
+        np.save(os.path.join(path, f"{prefix}{k}.npy"), np.ascontiguousarray(v))
+
+
 def segv_maps():
     """MZ_SEGV_MAPS=<file> (profiler-crash diagnosis only): on SIGSEGV the faulting address, PC,
     thread and /proc/self/maps go to <file> (scripts/segv_maps.c), then the profiler's own handler
@@ -683,9 +744,12 @@ def main():
             wsync = WeightSync(args, dev, stream if hip else None)
             wsync(0)  # (warm-up: the first sync allocates the collective's buffers)
             wsync.reset()
-        st0 = leg.stats() if hip and rank == 0 and not args.dropin else None
+        want_stats = args.full and hip and rank == 0 and not args.dropin  # (the roofline's counters)
+        st0 = leg.stats() if want_stats else None
         elapsed, own = timed(leg, args.steps, world, dist, sync, dev, wsync)
-        st1 = leg.stats() if hip and rank == 0 and not args.dropin else None
+        st1 = leg.stats() if want_stats else None
+        if args.dump_outputs and kind == order[0]:
+            dump_outputs(args.dump_outputs, leg.outputs(), prefix=f"rank{rank}_" if world > 1 else "")
         legs[kind] = dict(kind=kind, leg=leg, B=B, total=total, elapsed=elapsed, own=own, st0=st0, st1=st1,
                           broadcast=None if wsync is None else wsync.record(), wsync=wsync)
     # N > 1: every rank's device and its own step time, gathered to rank 0, and the collective's
@@ -701,10 +765,10 @@ def main():
     m = legs[main_kind]
     value = m["total"] * S * N * args.steps / m["elapsed"]
     roofline = None
-    if hip and rank == 0 and not args.dropin:
+    if args.full and hip and rank == 0 and not args.dropin:
         roofline = m["leg"].roofline(m["st0"], m["st1"], args.steps)
     cpu = None
-    if hip and rank == 0 and world == 1 and not args.no_cpu:
+    if args.full and hip and rank == 0 and world == 1 and not args.no_cpu:
         cpu = cpu_baseline(m["leg"].host_inputs, m["B"], A, K, S, N, args.cpu_seconds, args.cpu_procs,
                            ptree=args.map == "matrix")
 

@@ -11,8 +11,8 @@ IFS=';' read -ra CFGS <<< "$CONFIGS"
 for rep in 1 2; do
   for cfg in "${CFGS[@]}"; do
     n=${cfg%%:*}; a=${cfg#*:}
-    timeout -k 10 200 python bench.py --no-cpu $a > $O/new_${n}_$rep.json 2>/dev/null || exit 1
-    MZ_LIB_OVERRIDE=$ALT timeout -k 10 200 python bench.py --no-cpu $a > $O/alt_${n}_$rep.json 2>/dev/null || exit 1
+    timeout -k 10 200 python bench.py --full --no-cpu $a > $O/new_${n}_$rep.json 2>/dev/null || exit 1
+    MZ_LIB_OVERRIDE=$ALT timeout -k 10 200 python bench.py --full --no-cpu $a > $O/alt_${n}_$rep.json 2>/dev/null || exit 1
     echo "$n rep$rep new $(grep -o '"avg_launch_us": [0-9.]*' $O/new_${n}_$rep.json | cut -d' ' -f2) alt $(grep -o '"avg_launch_us": [0-9.]*' $O/alt_${n}_$rep.json | cut -d' ' -f2)"
   done
 done

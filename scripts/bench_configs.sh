@@ -1,11 +1,12 @@
 #!/bin/bash
 # bench.py over the BASELINE.json configurations that fit one GPU (one JSON line each).
 cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}" || exit 2
-mkdir -p gpurun_out
-out=gpurun_out/bench_configs.jsonl
+O=${MZ_OUT_DIR:-bench_out}  # where the logs and result lines go
+mkdir -p "$O"
+out=$O/bench_configs.jsonl
 : > "$out"
 run() {
-    timeout -k 10 300 python bench.py "$@" >> "$out" 2> gpurun_out/bench_configs.err || exit $?
+    timeout -k 10 300 python bench.py --full "$@" >> "$out" 2> $O/bench_configs.err || exit $?
 }
 run --map 3m --roots 256 --sims 50 --sampled-times 1
 run --map 3m --roots 256 --sims 50 --sampled-times 5

@@ -49,17 +49,17 @@ for c in $CONFIGS; do
     # --no-graph, the same kernels)
     ps="--steps 3 --warmup 1"; case $c in 27m*) ps="--steps 1 --warmup 1 --no-graph";; esac
     step "$d/pmc_fetch.json" 300 rocprofv3 --pmc FETCH_SIZE --output-format csv -d "$R/$d/pmc_fetch" -o run -- \
-        python3 "$R/bench.py" --no-cpu $ps $a
+        python3 "$R/bench.py" --full --no-cpu $ps $a
     step "$d/pmc_write.json" 300 rocprofv3 --pmc WRITE_SIZE --output-format csv -d "$R/$d/pmc_write" -o run -- \
-        python3 "$R/bench.py" --no-cpu $ps $a
+        python3 "$R/bench.py" --full --no-cpu $ps $a
     step "$d/pmc_summary.txt" 120 python scripts/pmc_summary.py "$d/pmc_fetch" "$d/pmc_write" --bench-args "$a" \
         --out gpurun_out/pmc_latest.json
     cp gpurun_out/pmc_latest.json profiles/pmc_latest.json
-    step "$d/bench.json" 300 python bench.py $a $cpu
+    step "$d/bench.json" 300 python bench.py --full $a $cpu
     # (MZ_TRACE_MARKS: fill kernels just outside the timed region, so trace_window.py can cut it out)
     export MZ_TRACE_MARKS=1
     step "$d/traced.json" 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$R/$d/trace" -o run -- \
-        python3 "$R/bench.py" --no-cpu $a
+        python3 "$R/bench.py" --full --no-cpu $a
     unset MZ_TRACE_MARKS
     python scripts/trace_window.py "$d/trace" --bench "$d/traced.json" --out "$d/window.json" > /dev/null || exit 3
     # keep the summaries: per-dispatch traces and counter dumps of the 27m workloads are > 64 MiB

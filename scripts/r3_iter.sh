@@ -23,7 +23,7 @@ PY
 }
 run() {  # name timeout args...
     local name=$1 to=$2; shift 2
-    timeout -k 10 "$to" python bench.py --no-cpu "$@" > $O/$name.json 2> $O/$name.err
+    timeout -k 10 "$to" python bench.py --full --no-cpu "$@" > $O/$name.json 2> $O/$name.err
     local rc=$?; [ $rc -ne 0 ] && { echo "$name rc=$rc"; tail -5 $O/$name.err; exit $rc; }
     return 0
 }

@@ -30,39 +30,39 @@ step() {  # name timeout cmd...
 }
 for s in $STEPS; do
   case $s in
-    headline) step headline 400 python bench.py ;;
-    strong)   for b in 32 64 128 256; do step roots_$b 200 python bench.py --no-cpu --roots $b; done ;;
-    k10)      step 3m_k10 200 python bench.py --no-cpu --sampled-times 10 &&
-              step 3s5z_k10 300 python bench.py --no-cpu --map 3s5z_vs_3s6z --roots 512 --sims 100 --sampled-times 10 ;;
+    headline) step headline 400 python bench.py --full ;;
+    strong)   for b in 32 64 128 256; do step roots_$b 200 python bench.py --full --no-cpu --roots $b; done ;;
+    k10)      step 3m_k10 200 python bench.py --full --no-cpu --sampled-times 10 &&
+              step 3s5z_k10 300 python bench.py --full --no-cpu --map 3s5z_vs_3s6z --roots 512 --sims 100 --sampled-times 10 ;;
     spans)    export MZ_STAMPS=1
-              step spans_3m_k1 200 python bench.py --no-cpu &&
-              step spans_3m_k5 200 python bench.py --no-cpu --sampled-times 5
+              step spans_3m_k1 200 python bench.py --full --no-cpu &&
+              step spans_3m_k5 200 python bench.py --full --no-cpu --sampled-times 5
               unset MZ_STAMPS ;;
     trace)    export MZ_TRACE_MARKS=1
               step traced_3m_k1 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$R/$O/trace_3m_k1" -o run -- \
-                  python3 "$R/bench.py" --no-cpu
+                  python3 "$R/bench.py" --full --no-cpu
               unset MZ_TRACE_MARKS
               python scripts/trace_window.py $O/trace_3m_k1 --bench $O/traced_3m_k1.json --out $O/window_3m_k1.json > /dev/null || exit 3
               find $O/trace_3m_k1 -name "*kernel_trace.csv" -size +30M -delete ;;
     search)   step search 900 python bench_search.py ${SEARCH_ARGS} ;;
-    matrix)   step matrix_k1 300 python bench.py --map matrix --roots 8 --sims 25 --sampled-times 1 --steps 50 --cpu-seconds 4 &&
-              step matrix_k3 300 python bench.py --map matrix --roots 8 --sims 25 --sampled-times 3 --steps 50 --cpu-seconds 4 ;;
+    matrix)   step matrix_k1 300 python bench.py --full --map matrix --roots 8 --sims 25 --sampled-times 1 --steps 50 --cpu-seconds 4 &&
+              step matrix_k3 300 python bench.py --full --map matrix --roots 8 --sims 25 --sampled-times 3 --steps 50 --cpu-seconds 4 ;;
     memset)   # the runtime defect behind round 1's graph failure: default packet capture, then off
               timeout -k 10 200 python -u scripts/memset_graph_repro.py 600 6 > $O/memset_repro_default.log 2>&1
               echo "memset repro (default) rc=$?"; tail -3 $O/memset_repro_default.log
               DEBUG_CLR_GRAPH_PACKET_CAPTURE=0 timeout -k 10 200 python -u scripts/memset_graph_repro.py 600 6 \
                   > $O/memset_repro_pc0.log 2>&1
               echo "memset repro (packet capture off) rc=$?"; tail -3 $O/memset_repro_pc0.log ;;
-    dropin)   step dropin_3m_k1 300 python bench.py --dropin --steps 5 --warmup 1 --no-cpu &&
-              step dropin_3m_k5 300 python bench.py --dropin --steps 5 --warmup 1 --no-cpu --sampled-times 5 ;;
+    dropin)   step dropin_3m_k1 300 python bench.py --full --dropin --steps 5 --warmup 1 --no-cpu &&
+              step dropin_3m_k5 300 python bench.py --full --dropin --steps 5 --warmup 1 --no-cpu --sampled-times 5 ;;
     pytest)   timeout -k 10 900 python -u -m pytest tests -m gpu -x -q -p no:cacheprovider --timeout 300 \
                   --timeout-method thread > $O/pytest_gpu.log 2>&1
               rc=$?; echo "pytest rc=$rc"; tail -3 $O/pytest_gpu.log; [ $rc -ne 0 ] && exit $rc ;;
     spansv)   export MZ_LIB_OVERRIDE=$R/mazero_amd/_build/variant_spans.so MZ_TRACE_MARKS=1
-              step spansv_3m_k1 200 python bench.py --no-cpu &&
-              step spansv_3m_k5 200 python bench.py --no-cpu --sampled-times 5 &&
+              step spansv_3m_k1 200 python bench.py --full --no-cpu &&
+              step spansv_3m_k5 200 python bench.py --full --no-cpu --sampled-times 5 &&
               step spansv_traced_3m_k1 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$R/$O/trace_spansv_3m_k1" \
-                  -o run -- python3 "$R/bench.py" --no-cpu
+                  -o run -- python3 "$R/bench.py" --full --no-cpu
               unset MZ_LIB_OVERRIDE MZ_TRACE_MARKS
               python scripts/trace_window.py $O/trace_spansv_3m_k1 --bench $O/spansv_traced_3m_k1.json \
                   --out $O/window_spansv_3m_k1.json > /dev/null || exit 3 ;;

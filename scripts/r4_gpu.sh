@@ -29,15 +29,15 @@ for st in $STEPS; do
         pytest) run pytest_gpu 900 python -u -m pytest tests -m gpu -x -q -p no:cacheprovider --timeout 300 \
                     --timeout-method thread ${PYTEST_ARGS} ;;
         smoke) run smoke 300 python -c "import __graft_entry__ as g; g.smoke()" ;;
-        bench) run bench 400 python bench.py ;;
+        bench) run bench 400 python bench.py --full ;;
         configs)
             IFS=';' read -ra CS <<< "${CONFIGS:-3m_k5:--sampled-times 5;3m_k10:--sampled-times 10;3s5z_k5:--map 3s5z_vs_3s6z --roots 512 --sims 100 --sampled-times 5;27m_k5:--map 27m_vs_30m --sims 200 --sampled-times 5}"
             for c in "${CS[@]}"; do
-                run "cfg_${c%%:*}" 400 python bench.py --no-cpu ${c#*:}
+                run "cfg_${c%%:*}" 400 python bench.py --full --no-cpu ${c#*:}
             done ;;
         dropin)
-            run dropin_k1 400 python bench.py --dropin --no-cpu --steps 10
-            run dropin_k5 400 python bench.py --dropin --no-cpu --steps 10 --sampled-times 5
+            run dropin_k1 400 python bench.py --full --dropin --no-cpu --steps 10
+            run dropin_k5 400 python bench.py --full --dropin --no-cpu --steps 10 --sampled-times 5
             run dropin_split 300 python scripts/dropin_split.py
             MZ_HOST_COPY=1 run dropin_split_copy 300 python scripts/dropin_split.py ;;
         ab)  # interleaved A/B of the product against each build in ALTS (default: the round-3 build)
@@ -47,8 +47,8 @@ for st in $STEPS; do
                 cat gpurun_out/ab_$alt.log
             done ;;
         stamps)  # per-phase cycles (MZ_STAMPS=1 diagnostic build) for K = 1 and K = 5
-            MZ_STAMPS=1 run stamps_k1 300 python bench.py --no-cpu --steps 5
-            MZ_STAMPS=1 run stamps_k5 300 python bench.py --no-cpu --steps 5 --sampled-times 5 ;;
+            MZ_STAMPS=1 run stamps_k1 300 python bench.py --full --no-cpu --steps 5
+            MZ_STAMPS=1 run stamps_k5 300 python bench.py --full --no-cpu --steps 5 --sampled-times 5 ;;
         micro)  # launch period against grid / workgroup size (scripts/gridsize.hip, built beforehand)
             run gridsize 120 ./scripts/_gridsize ;;
         search)

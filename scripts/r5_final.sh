@@ -8,5 +8,5 @@ timeout -k 10 1000 python -u -m pytest tests -m gpu -x -q -p no:cacheprovider --
   > $O/pytest_gpu.log 2>&1; rc=$?; echo "pytest rc=$rc"; tail -3 $O/pytest_gpu.log; [ $rc -ne 0 ] && exit $rc
 timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.log 2>&1; rc=$?; echo "smoke rc=$rc"; tail -2 $O/smoke.log
 [ $rc -ne 0 ] && exit $rc
-timeout -k 10 600 python bench.py > $O/bench_default.json 2> $O/bench_default.err; rc=$?; echo "bench rc=$rc"; cat $O/bench_default.json
+timeout -k 10 600 python bench.py --full > $O/bench_default.json 2> $O/bench_default.err; rc=$?; echo "bench rc=$rc"; cat $O/bench_default.json
 exit $rc

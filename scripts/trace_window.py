@@ -1,6 +1,6 @@
 """Cut bench.py's timed region out of a rocprofv3 kernel trace and summarise it.
 
-    MZ_TRACE_MARKS=1 rocprofv3 --kernel-trace --stats --output-format csv -d DIR -o run -- python3 bench.py ...
+    MZ_TRACE_MARKS=1 rocprofv3 --kernel-trace --stats --output-format csv -d DIR -o run -- python3 bench.py --full ...
     python scripts/trace_window.py DIR --bench traced.json [--out window.json]
 
 With MZ_TRACE_MARKS=1, bench.py launches a one-element int16 fill (FillFunctor<short>) just before

@@ -7,6 +7,7 @@ import os
 import sys
 
 import numpy as np
+import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -18,6 +19,116 @@ def test_defaults_are_the_headline_config():
     a = bench.parse([])
     assert (a.map, a.roots, a.sims, a.sampled_times) == ("3m", 256, 50, 1)
     assert not a.strong and not a.no_graph and a.broadcast_every == 0
+    # a plain run measures the headline figure only; nothing is written unless asked for
+    assert not a.full and a.dump_outputs is None
+    assert bench.parse(["--full", "--dump-outputs", "d"]).full
+
+
+def _run_main(monkeypatch, capsys, argv):
+    """bench.main() in this process with `argv`; the JSON line it printed."""
+    import json
+
+    import bench
+
+    for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK"):
+        monkeypatch.delenv(k, raising=False)
+    monkeypatch.setattr(sys, "argv", ["bench.py", *argv])
+    capsys.readouterr()
+    bench.main()
+    lines = [x for x in capsys.readouterr().out.splitlines() if x.startswith("{")]
+    assert len(lines) == 1
+    return json.loads(lines[0])
+
+
+def _load_dump(d):
+    return {f[:-4]: np.load(os.path.join(d, f)) for f in sorted(os.listdir(d))}
+
+
+def _expected_searches(port_lib, seed, B, A, S, N, K=1):
+    """The port's outputs for the inputs bench.py generates at --seed (rank 0 of a one-rank job)."""
+    from mazero_amd.cytree import Tree_batch
+    from mazero_amd.synthetic import DEFAULTS, make_search_inputs, run_search
+
+    d = DEFAULTS
+    rng = np.random.default_rng(seed * 1000)
+    out = []
+    for inp in [make_search_inputs(rng, B, A, S) for _ in range(N)]:
+        tb = Tree_batch(B, 1, A, K, S, d["delta_lb"], inp.seed, d["rho"], d["lam"], lib=port_lib)
+        out.append(run_search(tb, inp, K, per_sim=False))
+    return out
+
+
+def test_dump_outputs_files(tmp_path, monkeypatch):
+    """--dump-outputs writes float arrays; past the size limit, the same seeded sample every time."""
+    import bench
+
+    arrays = dict(a=np.arange(12, dtype=np.int32).reshape(3, 4), b=np.linspace(0, 1, 5000, dtype=np.float32),
+                  c=np.ones(3, np.float64))
+    bench.dump_outputs(str(tmp_path / "all"), arrays)
+    got = _load_dump(str(tmp_path / "all"))
+    assert sorted(got) == ["a", "b", "c"]
+    assert got["a"].dtype == np.float32 and got["a"].shape == (3, 4) and np.array_equal(got["a"], arrays["a"])
+    assert got["b"].dtype == np.float32 and np.array_equal(got["b"], arrays["b"]) and got["c"].dtype == np.float64
+    monkeypatch.setattr(bench, "DUMP_LIMIT", 3000)
+    bench.dump_outputs(str(tmp_path / "s1"), arrays)
+    bench.dump_outputs(str(tmp_path / "s2"), arrays, prefix="rank1_")
+    s1, s2 = _load_dump(str(tmp_path / "s1")), _load_dump(str(tmp_path / "s2"))
+    assert sorted(s2) == ["rank1_a", "rank1_b", "rank1_c"]
+    assert sum(v.nbytes for v in s1.values()) <= 3000
+    assert s1["b"].shape == (250,) and np.isin(s1["b"], arrays["b"]).all() and len(set(s1["b"])) == 250
+    assert np.array_equal(s1["b"], s2["rank1_b"]) and np.array_equal(s1["a"], arrays["a"])
+
+
+def test_plain_run_dumps_its_outputs(port_lib, tmp_path, monkeypatch, capsys):
+    """A plain run (here on the CPU port) times exactly --steps steps, measures nothing else, and
+    --dump-outputs writes the last step's search outputs: the same in two runs, and the port's own."""
+    B, S, N, A = 8, 6, 3, 9
+    argv = ["--gpus", "1", "--backend", "port", "--roots", str(B), "--sims", str(S), "--steps", "3", "--warmup", "1",
+            "--seed", "2"]
+    line = _run_main(monkeypatch, capsys, argv + ["--dump-outputs", str(tmp_path / "a")])
+    assert line["steps"] == 3 and line["ms_per_step"] > 0 and line["value"] > 0
+    # value = simulations of one step / ms_per_step (both rounded: 0.1 sims/s, 1e-4 ms)
+    assert abs(line["value"] * line["ms_per_step"] * 1e-3 / (B * S * N) - 1) <= 1e-4 / line["ms_per_step"] + 1e-3
+    assert line["roofline"] is None and line["cpu_baseline"] is None
+    _run_main(monkeypatch, capsys, argv + ["--dump-outputs", str(tmp_path / "b")])
+    a, b = _load_dump(str(tmp_path / "a")), _load_dump(str(tmp_path / "b"))
+    assert sorted(a) == [f"search{i}_values" for i in range(N)] and sorted(b) == sorted(a)
+    exp = _expected_searches(port_lib, 2, B, A, S, N)
+    for i in range(N):
+        v = a[f"search{i}_values"]
+        assert v.dtype == np.float32 and v.shape == (B,)
+        assert np.array_equal(v.view(np.uint32), b[f"search{i}_values"].view(np.uint32))
+        assert np.array_equal(v.view(np.uint32), np.asarray(exp[i]["root_values"], np.float32).view(np.uint32))
+
+
+@pytest.mark.gpu
+def test_gpu_run_dumps_its_outputs(port_lib, tmp_path, monkeypatch, capsys):
+    """The timed HIP path at a small size (16 roots x 8 sims, graph replay): a plain run carries no
+    roofline or CPU leg, --dump-outputs writes the last timed step's outputs -- bit for bit the CPU
+    port's values, visit counts and last selection -- and a second run writes the same files, the
+    gathered hidden states included.  --full --no-cpu adds the roofline."""
+    B, S, N, A = 16, 8, 3, 9
+    argv = ["--gpus", "1", "--roots", str(B), "--sims", str(S), "--steps", "2", "--warmup", "1", "--seed", "3"]
+    line = _run_main(monkeypatch, capsys, argv + ["--dump-outputs", str(tmp_path / "a")])
+    assert line["steps"] == 2 and line["ms_per_step"] > 0 and line["config"]["graph"]
+    assert line["roofline"] is None and line["cpu_baseline"] is None
+    _run_main(monkeypatch, capsys, argv + ["--dump-outputs", str(tmp_path / "b")])
+    a, b = _load_dump(str(tmp_path / "a")), _load_dump(str(tmp_path / "b"))
+    names = ("values", "marginal_visit_count", "sel_idx", "sel_idy", "sel_act", "leaf")
+    assert sorted(a) == sorted(f"search{i}_{n}" for i in range(N) for n in names) and sorted(b) == sorted(a)
+    for k in a:
+        assert a[k].dtype == np.float32 and np.array_equal(a[k].view(np.uint32), b[k].view(np.uint32)), k
+    exp = _expected_searches(port_lib, 3, B, A, S, N)
+    for i, e in enumerate(exp):
+        assert np.array_equal(a[f"search{i}_values"].view(np.uint32),
+                              np.asarray(e["root_values"], np.float32).view(np.uint32))
+        assert np.array_equal(a[f"search{i}_marginal_visit_count"], np.asarray(e["marginal_visit_count"]))
+        assert np.array_equal(a[f"search{i}_sel_idx"], e["sel_idx"][S - 1])
+        assert np.array_equal(a[f"search{i}_sel_act"][:, 0], e["sel_act"][S - 1])
+        assert np.array_equal(a[f"search{i}_sel_idy"], np.arange(B))
+        assert a[f"search{i}_leaf"].shape == (B, N * 128) and np.isfinite(a[f"search{i}_leaf"]).all()
+    full = _run_main(monkeypatch, capsys, argv + ["--full", "--no-cpu"])
+    assert full["roofline"]["achieved"] > 0 and full["cpu_baseline"] is None
 
 
 def test_cpu_baseline_fields(port_lib):
