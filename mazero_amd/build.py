@@ -35,7 +35,8 @@ FLAGS = [
     "-fno-fast-math",
     "-Wall",
     "-Wno-unused-function",
-    # the first 16 dwords of scalar kernel arguments arrive in SGPRs at wave launch
+    # 16 user SGPRs for kernel-argument preloading: two hold the kernel-argument pointer, so the first
+    # 14 dwords of scalar kernel arguments arrive in SGPRs at wave launch
     "-mllvm",
     "-amdgpu-kernarg-preload-count=16",
 ]

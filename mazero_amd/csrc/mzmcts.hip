@@ -761,8 +761,11 @@ __device__ __forceinline__ double cdf_lane(double bd, int A) {
 // instead of v_readlane.  N terms (A <= N): trailing +0.0 terms are exact no-ops on the
 // non-negative sums, so N only has to cover A -- the class (4, 8, 12, 16) is picked once per call,
 // not per term.  Lane a returns cp[a] (cp[A-1] forced to 1.0).
-template <int N>
-__device__ __forceinline__ double cdf_terms(int A, const float *sw, double *sp, float wl) {
+struct NoWork {
+    __device__ void operator()() const {}
+};
+template <int N, class F2 = NoWork>
+__device__ __forceinline__ double cdf_terms(int A, const float *sw, double *sp, float wl, F2 &&during2 = F2()) {
     const int l = lane_id();
     float w[N];
 #pragma unroll
@@ -778,6 +781,7 @@ __device__ __forceinline__ double cdf_terms(int A, const float *sw, double *sp, 
     for (int j = 0; j < N; ++j) sum += (double)w[j];
     const double p = (l < A) ? (double)wl / sum : 0.0;
     sp[l] = p;
+    during2();
     wait_lds();
     double pj[N];
 #pragma unroll
@@ -797,7 +801,8 @@ __device__ __forceinline__ double cdf_terms(int A, const float *sw, double *sp, 
 }
 // A > 16: batches of 16 terms, then the rest in steps of 4 up to A rounded up to 4 (27m: 36 terms,
 // not three batches of 16); each batch's LDS reads issued together ahead of its adds
-__device__ __forceinline__ double cdf_long(int A, const float *sw, double *sp, float wl) {
+template <class F2 = NoWork>
+__device__ __forceinline__ double cdf_long(int A, const float *sw, double *sp, float wl, F2 &&during2 = F2()) {
     const int l = lane_id();
     const int A4 = (A + 3) & ~3;
     double sum = 0.0;
@@ -840,6 +845,7 @@ __device__ __forceinline__ double cdf_long(int A, const float *sw, double *sp, f
     }
     const double p = (l < A) ? (double)wl / sum : 0.0;
     sp[l] = p;
+    during2();
     wait_lds();
     double acc = 0.0, cp = 0.0;
     a0 = 0;
@@ -898,21 +904,20 @@ __device__ __forceinline__ double cdf_staged(int A, const float *sw, double *sp)
     return cdf_long(A, sw, sp, wl);
 }
 // the same for the weights bet held one per lane (lane a < A); `during` runs while the weights'
-// LDS store is in flight (independent per-lane work of the caller)
-struct NoWork {
-    __device__ void operator()() const {}
-};
-template <class F = NoWork>
-__device__ __forceinline__ double cdf_bcast(float bet, int A, float *sw, double *sp, F &&during = F()) {
+// LDS store is in flight, `during2` while the probabilities' is (independent work of the caller:
+// what it must not leave to the compiler's placement it pins with an empty asm volatile)
+template <class F = NoWork, class F2 = NoWork>
+__device__ __forceinline__ double cdf_bcast(float bet, int A, float *sw, double *sp, F &&during = F(),
+                                            F2 &&during2 = F2()) {
     const int l = lane_id();
     sw[l] = (l < A) ? bet : 0.f;  // kMaxActions = kWave entries
     during();
     wait_lds();
-    if (A <= 4) return cdf_terms<4>(A, sw, sp, bet);
-    if (A <= 8) return cdf_terms<8>(A, sw, sp, bet);
-    if (A <= 12) return cdf_terms<12>(A, sw, sp, bet);
-    if (A <= 16) return cdf_terms<16>(A, sw, sp, bet);
-    return cdf_long(A, sw, sp, bet);
+    if (A <= 4) return cdf_terms<4>(A, sw, sp, bet, during2);
+    if (A <= 8) return cdf_terms<8>(A, sw, sp, bet, during2);
+    if (A <= 12) return cdf_terms<12>(A, sw, sp, bet, during2);
+    if (A <= 16) return cdf_terms<16>(A, sw, sp, bet, during2);
+    return cdf_long(A, sw, sp, bet, during2);
 }
 
 // --------------------------------------------------------------------------------------------
@@ -2337,7 +2342,7 @@ __device__ __forceinline__ void select_walk(const Geo &g, const Dev &d, Lds &s, 
 // value entries the back-propagation needs, in flight while the leaf is expanded.
 // --------------------------------------------------------------------------------------------
 // Scalar arguments, the ones each wave needs first leading: with kernel-argument preloading
-// (-mllvm -amdgpu-kernarg-preload-count) the first 16 dwords arrive in SGPRs at wave launch, so the
+// (-mllvm -amdgpu-kernarg-preload-count) the first 14 dwords arrive in SGPRs at wave launch, so the
 // round-1 addresses do not wait for a kernel-argument load.
 template <bool EB, bool SEL, int NC, bool JOINT>
 __global__ __launch_bounds__(128) void k_step(char *base, int P, int PS, int BA, int pk, const float *reward,
@@ -3425,7 +3430,9 @@ struct Chain3Args {  // k_chain3's parameter list, for the kernel-argument offse
     const char *src_slot;
     ChainIO io;
 };
-// (the first 16 dwords, through src_slot, arrive preloaded in SGPRs)
+// (the first 14 dwords, through the discount, arrive preloaded in SGPRs: two of the 16 user SGPRs
+// hold the kernel-argument pointer.  src_slot is not among them: wave 2 fetches it with a scalar
+// load and waits for it before it issues the row's loads)
 static_assert(offsetof(Chain3Args, src_slot) == 56 && offsetof(Chain3Args, io) == 64 && sizeof(ChainIO) == 56,
               "k_chain3 argument layout");
 #ifdef __HIP_DEVICE_COMPILE__
@@ -3437,6 +3444,16 @@ typedef const ChainIO cChainIO;
 typedef int int4v __attribute__((ext_vector_type(4)));
 typedef int int8v __attribute__((ext_vector_type(8)));
 typedef int int16v __attribute__((ext_vector_type(16)));
+// stores through an address a lane holds in registers (typed as global memory: global_store, not flat)
+#ifdef __HIP_DEVICE_COMPILE__
+typedef __attribute__((address_space(1))) int4v g_int4v;
+typedef __attribute__((address_space(1))) int g_int;
+#else
+typedef int4v g_int4v;
+typedef int g_int;
+#endif
+__device__ __forceinline__ void st_lane16(uintptr_t p, int4v v) { *(g_int4v *)p = v; }
+__device__ __forceinline__ void st_lane4(uintptr_t p, int v) { *(g_int *)p = v; }
 // scalar loads issued here and waited for by swait (invisible to the compiler's wait counting, which
 // stays correct: its own LDS waits only ever wait longer with more loads outstanding)
 __device__ __forceinline__ int sload1(const void *p) {
@@ -3487,8 +3504,9 @@ int chain3_lds_bytes(int nc) { return Chain3Layout<0>(nc).total; }
 
 // ROW: the leaf-row gather's class -- 0 any row, 1 16-byte aligned rows of <= 4 KiB (registers), 2
 // aligned rows of <= 16 KiB (LDS-DMA), 3 no gather (no pool, or no selection).  For ROW 1 and 2 the
-// host passes the leaf's slot (pool + hsx * pool_stride) in the preloaded argument src_slot and the
-// row size in 16-byte units in ppk's top bits: wave 2 issues the row's loads at its first instruction.
+// host passes the leaf's slot (pool + hsx * pool_stride) in the argument src_slot (the first one past
+// the preloaded 14 dwords: one scalar load) and the row size in 16-byte units in the preloaded ppk's
+// top bits: wave 2 issues the row's loads as soon as src_slot has landed, ahead of its scalar round.
 template <int NC, bool SEL, int ROW>
 __global__ __launch_bounds__(192) void k_chain3(char *base, const float *policy, const float *beta, const float *reward,
                                                 const float *value, int ppk, int bak, int hsx, float discount,
@@ -3676,7 +3694,7 @@ __global__ __launch_bounds__(192) void k_chain3(char *base, const float *policy,
         // Straight-line code in issue order (the row class ROW is a template argument): every wait
         // the compiler places then counts exactly the loads issued after the one it needs.
         // The row of this launch's leaf (hidden_state_index_x = hsx) is issued first, from preloaded
-        // arguments only (ROW 1, 2); then one scalar round trip: the outputs' kernel arguments, the
+        // arguments and src_slot's own scalar load (ROW 1, 2); then one scalar round trip: the outputs' kernel arguments, the
         // header, the handle's constants.  This wave takes no barrier: nothing it does is read by
         // another wave, and s_barrier waits only for the workgroup's waves that have not ended.
         const long long o = (long long)l * 16;
@@ -3786,6 +3804,18 @@ __global__ __launch_bounds__(192) void k_chain3(char *base, const float *policy,
     int omri = sload1(&pl->g.one_minus_rho), gWi = sload1(&pl->g.W), oRi = sload1(&pl->d.o_R);
     const float pol = policy[(size_t)t * A + (l < A ? l : 0)];
     const float bet = beta[(size_t)t * A + (l < A ? l : 0)];
+    // This launch's record stores, one per lane, from addresses held in registers: lane 0 the child's
+    // C, lane 1 the leaf's Bn, lane 2 the child's A, lane 3 the child's Bn (16 bytes each), and the
+    // dwords of lane 0 the child's PP, lanes 1-3 idx_x / idy / act.  The node addresses follow from
+    // the preloaded arguments (the leaf of an in-sequence launch is hsx): computed here, while round
+    // 1's loads are in flight, in vector registers (the scalar file is full).
+    unsigned oA = d.o_A, oBn = d.o_Bn, oC = d.o_C;
+    asm volatile("" : "+s"(oA), "+s"(oBn), "+s"(oC));  // (values, not fields: no table in scratch)
+    const unsigned o16 = (l == 0) ? oC : (l == 2) ? oA : oBn;
+    const uintptr_t abase = (uintptr_t)d.base;
+    uintptr_t p16 = abase + (size_t)o16 * 256 + (nb + (size_t)Dp + (l == 1 ? 0 : 1)) * 16;
+    uintptr_t p4 = abase + (size_t)d.o_PP * 256 + (nb + (size_t)Dp + 1) * 4;
+    asm volatile("" : "+v"(p16), "+v"(p4));
     asm volatile("s_waitcnt lgkmcnt(0)"
                  : "+s"(hv), "+s"(root_vis0), "+s"(r_i), "+s"(v_i), "+s"(lb), "+s"(io_xy), "+s"(io_a), "+s"(omri),
                    "+s"(gWi), "+s"(oRi)
@@ -3839,61 +3869,100 @@ __global__ __launch_bounds__(192) void k_chain3(char *base, const float *policy,
             }
             return;
         }
-        leaf_b = d.Bn()[nb + D];  // out of sequence: the header's leaf
+        // out of sequence: the header's leaf (waited for here: no wait for it on the path in sequence)
+        leaf_b = uni4(d.Bn()[nb + D]);
+        p16 += (long long)(D - Dp) * 16;
+        p4 += (long long)(D - Dp) * 4;
     }
     stamp(ts, 1);
-    int err = 0;
     const int leaf = D, c = D + 1;  // the new child
     int cursor = h.cursor;
     int a = 0;
     const float bh = 1.0f;  // betahat_prob = count / sampled_times = 1 / 1
-    // every lane's prior * betahat_prob / beta_prob (eps = 0 after the root), computed while the
-    // distribution's first LDS store is in flight; the drawn lane's is read after the draw
+    // ---- everything the draw does not feed, before the draw ----
+    // The errors but kErrTable's bit: the records are created unless err1, the outputs report a
+    // selection unless any error -- and whether there is one is known here (kErrTable depends on the
+    // draw only when another error is set already).
+    const float omr = i2f(omri);
+    const int Ds = c;
+    int err1 = (c + 1 > P) ? kErrPool : 0;
+    if (value_lim(1, omr) != 1) err1 |= kErrValueSet;  // (count 1: size_lim must be 1, utils.cpp:31)
+    int errp = err1;
+    if (SEL && Ds + 1 > PS) errp |= kErrPath;
+    // the root's total child visits after this back-propagation index the pUCT table (select_walk
+    // checks it in the fast case; in the exact case it is the largest parent count of the path)
+    const bool tbl = SEL && root_vis0 >= PS;
+    const bool any_err = errp != 0 || tbl;
+    const bool tame0 = h.tame && tame_val(v_in) && tame_val(r_in);
+    const int md = md_of(leaf_b.y) < 0 ? 0 : md_of(leaf_b.y);
+    // the records' words by lane (above); the drawn words -- lane 2's prior, lane 3's action and
+    // act[t] -- are set after the draw
+    int leaf_y = pack_y(1, act_of(leaf_b.y), md), idx_v = any_err ? 0 : hsx;  // (idx_x: the expanded leaf's)
+    asm volatile("" : "+s"(leaf_y), "+s"(idx_v));
+    int4v d16 = {l == 1 ? c : 0, l == 1 ? leaf_y : 0, l == 1 ? f2i(v_in) : 0, l == 1 ? hsx : (l == 3 ? -1 : 0)};
+    int d4 = (l == 0) ? f2i(v_in) : t;
+    d4 = (l == 1) ? idx_v : d4;
+    uintptr_t xp = (uintptr_t)((l == 1) ? idx_x : (l == 2) ? idy : act) + (size_t)t * 4;
+    p4 = (l == 0) ? p4 : xp;
+    const bool st16 = l < 2 && !err1, st4 = (l == 0) ? !err1 : (SEL && l < 3);
+    // the stores without a drawn word go first: C[gi], Bn[leaf], PP[gi], idx_x, idy
+    auto early = [&]() {
+        if (st16) st_lane16(p16, d16);
+        if (st4) st_lane4(p4, d4);
+        asm volatile("" : "+v"(p16), "+v"(p4), "+v"(d16) : : "memory");
+    };
+    // every lane's prior * betahat_prob / beta_prob (eps = 0 after the root) and whether it is tame:
+    // after the draw only the drawn lane's are read
     float prior_l = 0.f;
+    int wild_l = 0;
+    auto priors = [&]() {
+        prior_l = pol * bh / bet;
+        wild_l = tame_prior(prior_l) ? 0 : 1;
+        asm volatile("" : "+v"(prior_l), "+v"(wild_l));
+    };
     if (A >= 2) {
-        const double cp = cdf_bcast(bet, A, (float *)(smem + L.oW), (double *)(smem + L.oP),
-                                    [&]() { prior_l = pol * bh / bet; });
-        const double w1 = (double)h.nxt[0], w2 = (double)h.nxt[1];
-        double u = (w1 + w2 * 4294967296.0) / 18446744073709551616.0;
-        if (u >= 1.0) u = 0x1.fffffffffffffp-1;  // nextafter(1, 0)
-        a = __popcll(ballot(l < A && cp < u));    // lower_bound
+        // the draw's u, from the header's two engine words
+        double u = 0.0;
+        const double cp = cdf_bcast(
+            bet, A, (float *)(smem + L.oW), (double *)(smem + L.oP),
+            [&]() {  // (while the distribution's first LDS store is in flight)
+                priors();
+                early();
+            },
+            [&]() {  // (while its second is)
+                const double w1 = (double)h.nxt[0], w2 = (double)h.nxt[1];
+                u = (w1 + w2 * 4294967296.0) / 18446744073709551616.0;
+                if (u >= 1.0) u = 0x1.fffffffffffffp-1;  // nextafter(1, 0)
+                asm volatile("" : "+v"(u));
+            });
+        a = __popcll(ballot(l < A && cp < u));  // lower_bound
         cursor += 2;
     } else {
-        prior_l = pol * bh / bet;
+        priors();
+        early();
     }
     a = uni(a);
     stamp(ts, 2);
-    const float omr = i2f(omri);
-    if (c + 1 > P) err |= kErrPool;
-    if (value_lim(1, omr) != 1) err |= kErrValueSet;  // (count 1: size_lim must be 1, utils.cpp:31)
-    const float pol_a = rlf(pol, a), bet_a = rlf(bet, a);
+    // ---- after the draw: the drawn lane's prior, the words it feeds, their stores ----
     const float prior = rlf(prior_l, a);
-    const bool wild = !tame_prior(prior);
-    leaf_b = uni4(leaf_b);
-    if (!err && l == 0) {
-        const size_t gi = nb + c;
-        d.A()[gi] = make_int4(0, f2i(prior), f2i(0.0f), f2i(0.0f));
-        d.Bn()[gi] = make_int4(0, pack_y(0, a, -1), f2i(0.0f), -1);
-        d.C()[gi] = make_float4(0.f, 0.f, 0.f, 0.f);
-        d.PP()[gi] = v_in;
-        if (leaf == 0) {  // (readbacks: root children)
-            d.o_D = pl->d.o_D;
-            d.D()[gi] = make_float4(pol_a, bet_a, bh, 0.f);
-        }
-        const int md = md_of(leaf_b.y) < 0 ? 0 : md_of(leaf_b.y);
-        d.Bn()[nb + leaf] = make_int4(c, pack_y(1, act_of(leaf_b.y), md), f2i(v_in), hsx);
-    }
-    const int tame = (h.tame && !wild && tame_val(v_in) && tame_val(r_in)) ? 1 : 0;
+    const bool wild = rl(wild_l, a) != 0;
+    const int tame = (tame0 && !wild) ? 1 : 0;
     const bool fast = !SEL || (fast_ok && tame && fabsf(discount) <= 1.0f);  // (no selection: no words)
-    const int Ds = c;
-    if (SEL && Ds + 1 > PS) err |= kErrPath;
-    // the root's total child visits after this back-propagation index the pUCT table (select_walk
-    // checks it in the fast case; in the exact case it is the largest parent count of the path)
-    if (SEL && root_vis0 >= PS && (fast || !err)) err |= kErrTable;
-    if (SEL && l == 0) {
-        idx_x[t] = err ? 0 : hsx;  // parent->hidden_state_index_x: the expanded leaf's
-        idy[t] = t;
-        act[t] = err ? 0 : a;
+    int err = errp;
+    if (tbl && (fast || !errp)) err |= kErrTable;
+    // The fast case's engine words have landed with the stores above (issued a distribution ago):
+    // one wait here, before this launch's last stores, instead of the compiler's after them
+    unsigned nxt_fast = (wi >= 0 && wi < gW) ? w_fast : 0u;  // (cursor + words + l == wi)
+    asm volatile("s_waitcnt vmcnt(0)" : "+v"(nxt_fast) : : "memory");
+    if (fast && l < kNxt) hp->nxt[l] = nxt_fast;
+    // (sel_lane: two v_cndmask; the compiler makes branches of the selects)
+    d16.y = f2i(sel_lane(sel_lane(i2f(d16.y), prior, 1ull << 2), i2f(pack_y(0, a, -1)), 1ull << 3));
+    if ((l == 2 || l == 3) && !err1) st_lane16(p16, d16);
+    if (SEL && l == 3) st_lane4(p4, any_err ? 0 : a);
+    if (!err1 && leaf == 0) {  // (readbacks: root children)
+        const float pol_a = rlf(pol, a), bet_a = rlf(bet, a);
+        d.o_D = pl->d.o_D;
+        if (l == 0) d.D()[nb + c] = make_float4(pol_a, bet_a, bh, 0.f);
     }
     stamp(ts, 3);
     // wave 1's back-propagation (sA, sPP) and min / max: read by the exact case and the fused
@@ -3943,13 +4012,9 @@ __global__ __launch_bounds__(192) void k_chain3(char *base, const float *policy,
         }
     }
     stamp(ts, 5);
-    if (l < kNxt) {
+    if (!fast && l < kNxt) {  // (the fast case's words: stored above)
         unsigned nxt_w = 0;
-        if (fast) {
-            nxt_w = (wi >= 0 && wi < gW) ? w_fast : 0u;  // (cursor + words + l == wi)
-        } else if (SEL && !err && cursor + words + l < gW) {
-            nxt_w = Rt[cursor + words + l];
-        }
+        if (SEL && !err && cursor + words + l < gW) nxt_w = Rt[cursor + words + l];
         hp->nxt[l] = nxt_w;
     }
     if (l == 0) {
@@ -6910,7 +6975,8 @@ void launch_chain3_row(mz_batch *b, const StepArgs &a) {
     const Dev &dv = b->dev;
     // (the first 14 argument dwords, through the discount, arrive preloaded in SGPRs)
     const ChainIO io{a.pool, a.pool_stride, a.row_bytes, a.gather_out, a.idx_x, a.idy, a.act};
-    // ROW 1, 2: the leaf's slot and the row size (16-byte units, <= 1024) ride in preloaded arguments
+    // ROW 1, 2: the row size (16-byte units, <= 1024) rides in the preloaded ppk, the leaf's slot in
+    // the first argument past the preloaded ones
     const bool pre = ROW == 1 || ROW == 2;
     const char *src_slot = pre ? a.pool + (long long)a.hsx * a.pool_stride : nullptr;
     const int rb16 = pre ? (int)(a.row_bytes / 16) : 0;
