@@ -770,6 +770,7 @@ __global__ __launch_bounds__(kHbmWaves * kWave) void k_hbm(const Params *__restr
         hp->mm_cnt = h.mm_cnt;
         hp->tame = h.tame;
         hp->leaf = h.leaf;
+        hp->hot_tag = 0;  // (k_chain3's copy of A[root].x / Bn[leaf].y: not maintained here)
     }
     stamp(ts, 5);
     long long *st = d.stats() + (size_t)t * MZ_S_COUNT;

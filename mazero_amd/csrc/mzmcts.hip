@@ -33,6 +33,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <cassert>
 #include <cmath>
 #include <cstdint>
 #include <cstdlib>
@@ -80,8 +81,21 @@ struct TreeHdr {
     // [0, 1e30]: then (with the handle's fast_ok conditions) no pUCT score can be NaN or below
     // FLOAT_MIN, so a K = 1 selection consumes one engine word per non-forced level (select_walk)
     int tame;
+    // A copy of two record words the next K = 1 launch would otherwise load (k_chain3): the root's
+    // visit count A[root].x and the leaf's Bn[leaf].y, valid while hot_tag == tot (the tot they were
+    // written at; a usable header has tot >= 1).  k_prepare and k_chain3 maintain them; every other
+    // writer of the header stores hot_tag = 0 (and every kernel that changes A[root].x or the leaf
+    // writes the header in the same launch).
+    int root_vis, leaf_y, hot_tag;
     unsigned nxt[kNxt];  // R[cursor .. cursor + kNxt): the next expansion's engine words
+    unsigned pad_[20];   // one header per 256-byte block (arena_nodes: tree t's header follows from t alone)
 };
+// The hot part -- cursor .. hot_tag and nxt[0 .. 3], what k_chain3's wave 0 fetches with one 16-dword
+// scalar load -- is the first 64-byte line of a 256-byte aligned block: the load never straddles lines.
+constexpr int kHdrHotWords = 16;
+static_assert(sizeof(TreeHdr) == 256 && offsetof(TreeHdr, root_vis) == 36 && offsetof(TreeHdr, nxt) == 48 &&
+                  offsetof(TreeHdr, nxt) + 4 * sizeof(unsigned) == 4 * kHdrHotWords,
+              "TreeHdr: 256-byte blocks, the hot words in the first 64-byte line");
 
 struct Geo {
     int B, A, K, S, P, E, W, PS;
@@ -182,18 +196,24 @@ __host__ __device__ __forceinline__ unsigned span_n(unsigned n, unsigned k = 0) 
     return n / (256 / c) + (c * (n % (256 / c)) + k + 64 + 255) / 256;
 }
 // (mz_create: B < 2^24, B * P < 2^32 and B * PS < 2^32, so every product below fits 32 bits)
-// The node arrays come first: their offsets then follow from B * P alone (k_chain3 computes them
-// with a dozen scalar instructions before its first load).
-__host__ __device__ __forceinline__ void arena_nodes(Dev &d, unsigned B, unsigned P) {
+// The tree headers come first, one 256-byte block each directly after Params: tree t's header is at
+// base + (kArenaHdr + t) * 256, three scalar instructions from k_chain3's preloaded arguments.  The
+// lambda-power table follows (wave 1's round 1 reads it: its offset follows from B), then the node
+// arrays, whose offsets follow from B, PS and B * P (computed while the header load is in flight).
+constexpr unsigned kArenaHdr = (unsigned)((sizeof(Params) + 64 + 255) / 256);
+__host__ __device__ __forceinline__ unsigned arena_lp(unsigned B) { return kArenaHdr + B + 1; }  // (span of B * 256 bytes)
+__host__ __device__ __forceinline__ void arena_nodes(Dev &d, unsigned B, unsigned P, unsigned PS) {
     const unsigned nodes = B * P;
     const unsigned s16 = span_n<16>(nodes), s4 = span_n<4>(nodes);
-    d.o_A = (unsigned)arena_span(sizeof(Params));
+    d.o_hdr = kArenaHdr;
+    d.o_lp = arena_lp(B);
+    d.o_A = d.o_lp + span_n<4>(PS + 1 + kWave);
     d.o_Par = d.o_A + s16;
     d.o_Bn = d.o_Par + s4;
     d.o_Q = d.o_Bn + s16;
     d.o_PP = d.o_Q + s4;
     d.o_C = d.o_PP + s4;
-    d.o_hdr = d.o_C + s16;
+    d.o_stats = d.o_C + s16;  // (what follows the node arrays: arena_hot)
 }
 // pUCT coefficient table entries, T[n (n + 1) / 2 + v] = pb_c(n, v) for n < PS, padded to 4.  Only
 // k_step's LDS-staged table (4 TT <= kTableLdsMax: PS <= 155) and k_tree's prior scores (value
@@ -206,13 +226,11 @@ __host__ __device__ __forceinline__ unsigned table_entries(unsigned PS) {
 }
 __host__ __device__ __forceinline__ void arena_hot(Dev &d, unsigned B, unsigned P, unsigned PS) {
     const unsigned TT = table_entries(PS);
-    arena_nodes(d, B, P);
-    unsigned o = d.o_hdr;
-    o += (B * (unsigned)sizeof(TreeHdr) + 64 + 255) / 256;
-    d.o_stats = o; o += span_n<8>(B * MZ_S_COUNT);
+    arena_nodes(d, B, P, PS);
+    unsigned o = d.o_stats;
+    o += span_n<8>(B * MZ_S_COUNT);
     d.o_err = o; o += span_n<4>(1);
     d.o_seed = o; o += span_n<4>(1);
-    d.o_lp = o; o += span_n<4>(PS + 1 + kWave);
     d.o_T = o; o += span_n<4>(TT + 4 * kWave);
     d.o_pb = o; o += span_n<4>(PS + kWave);
     d.o_sq = o; o += span_n<8>(PS + kWave);
@@ -1518,6 +1536,11 @@ __global__ __launch_bounds__(256) void k_prepare(const Params *__restrict__ prm,
         h.mm_cnt = 0;
         h.leaf = leaf;
         h.tame = (!wild && tame_val(v) && tame_val(r)) ? 1 : 0;
+        // the hot copy: the root has one visit; the leaf is the root (Bn[root].y as stored above) or,
+        // after the first selection, its first child (Bn.y as expand_node stores it)
+        h.root_vis = 1;
+        h.leaf_y = (D == 1) ? pack_y(0, first_act, -1) : pack_y(nc, 0, 0);
+        h.hot_tag = (!err && g.N == 1 && g.K == 1) ? tot : 0;
         for (int j = 0; j < kNxt; ++j) h.nxt[j] = (cursor + j < kMtN) ? w0[cursor + j] : 0u;
         d.hdr()[t] = h;
         d.path()[(size_t)t * g.PS] = make_int2(0, 1);
@@ -2860,6 +2883,7 @@ __global__ __launch_bounds__(128) void k_step(char *base, int P, int PS, int BA,
             hp->mm_cnt = h.mm_cnt;
             hp->tame = h.tame;
             hp->leaf = h.leaf;
+            hp->hot_tag = 0;  // (k_chain3's copy of A[root].x / Bn[leaf].y: not maintained here)
         }
     }
     if (gath_lds) {
@@ -3358,6 +3382,7 @@ __global__ __launch_bounds__(128) void k_chain(char *base, const float *policy, 
             hp->mm_cnt = mm_cnt;
             hp->tame = tame;
             hp->leaf = (err || !SEL) ? h.leaf : c;
+            hp->hot_tag = 0;  // (k_chain3's copy of A[root].x / Bn[leaf].y: not maintained here)
         }
     }
     stamp(ts, 7);
@@ -3409,18 +3434,35 @@ __global__ __launch_bounds__(128) void k_chain(char *base, const float *policy, 
 // Every error and output is decided from the same scalar inputs as k_chain: results are bit-identical.
 //
 // Launch arguments.  The first 14 dwords arrive preloaded in SGPRs; they hold everything round 1
-// addresses (the node arrays lead the arena, so their offsets follow from B and P: arena_nodes).
-// The outputs (ChainIO) are read through the kernel-argument
-// pointer by the waves that need them, where they need them: the compiler would otherwise load
-// every argument in the common prologue and wait there.  Round 1's scalar loads are issued by
-// inline assembly (sload*) and waited for with one explicit wait (swait): the compiler would sink
-// each load past the first branch after it.
+// addresses: tree t's header is a 256-byte block at a constant offset, the lambda-power table and
+// the node arrays follow at offsets computed from B, PS and B * P (arena_nodes) while the header
+// load is in flight.  The rest (ChainIO) is read through the kernel-argument pointer by the waves
+// that need it, where they need it: the compiler would otherwise load every argument in the common
+// prologue and wait there.  ChainIO is two 64-byte lines, one scalar load each: wave 2's (the row
+// gather's arguments) and wave 0's (the output pointers), each with the handle constants that role
+// would otherwise fetch from Params (ChainK, filled once at mz_create).  Wave 1 needs neither.
+// Round 1's scalar loads are issued by inline assembly (sload*) and waited for with one explicit
+// wait per role: the compiler would sink each load past the first branch after it.
 // --------------------------------------------------------------------------------------------
+struct ChainK {  // the Params fields wave 0 reads (mz_create checks them against Params)
+    float one_minus_rho;
+    int W;
+    unsigned o_R, o_err, o_D, o_stats;
+    float delta;
+    unsigned o_pb, o_sq;
+    int pad_;
+};
 struct ChainIO {
+    // wave 2's line
     const char *pool;
     long long pool_stride, row_bytes;
     char *gather_out;
+    float w2_one_minus_rho;
+    unsigned w2_o_stats;
+    int pad_[6];
+    // wave 0's line
     int *idx_x, *idy, *act;
+    ChainK k;
 };
 struct Chain3Args {  // k_chain3's parameter list, for the kernel-argument offset of ChainIO
     char *base;
@@ -3433,8 +3475,9 @@ struct Chain3Args {  // k_chain3's parameter list, for the kernel-argument offse
 // (the first 14 dwords, through the discount, arrive preloaded in SGPRs: two of the 16 user SGPRs
 // hold the kernel-argument pointer.  src_slot is not among them: wave 2 fetches it with a scalar
 // load and waits for it before it issues the row's loads)
-static_assert(offsetof(Chain3Args, src_slot) == 56 && offsetof(Chain3Args, io) == 64 && sizeof(ChainIO) == 56,
-              "k_chain3 argument layout");
+static_assert(offsetof(Chain3Args, src_slot) == 56 && offsetof(Chain3Args, io) == 64 && sizeof(ChainIO) == 128 &&
+                  offsetof(ChainIO, idx_x) == 64 && sizeof(ChainK) == 40,
+              "k_chain3 argument layout: one 64-byte line per role");
 #ifdef __HIP_DEVICE_COMPILE__
 typedef const __attribute__((address_space(4))) ChainIO cChainIO;
 #else
@@ -3517,10 +3560,15 @@ __global__ __launch_bounds__(192) void k_chain3(char *base, const float *policy,
     constexpr Chain3Layout<NC> L(NC);
     const int P = ppk & 0x3ff, PS = (ppk >> 10) & 0x3ff;
     const int A = (bak >> 24) & 0x7f, fast_ok = (int)((unsigned)bak >> 31);
-    const int B = bak & 0xffffff;
     Dev d;
     d.base = (gchar *)base;
-    arena_nodes(d, B, P);
+    // the node arrays' offsets, computed by each role after it has issued its header load (the
+    // empty asm orders the arithmetic behind the loads' asm statements)
+    auto arena = [&]() {
+        int bk = bak, pk = ppk;
+        asm volatile("" : "+s"(bk), "+s"(pk));
+        arena_nodes(d, (unsigned)bk & 0xffffffu, (unsigned)pk & 0x3ffu, ((unsigned)pk >> 10) & 0x3ffu);
+    };
     cChainIO *iop = (cChainIO *)((const char *)__builtin_amdgcn_kernarg_segment_ptr() + offsetof(Chain3Args, io));
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     float *sX = (float *)(smem + L.oX);
@@ -3537,15 +3585,16 @@ __global__ __launch_bounds__(192) void k_chain3(char *base, const float *policy,
     unsigned long long ts[8] = {0};
     stamp(ts, 0);
     const unsigned long long rt0 = span_open();
+    d.o_hdr = kArenaHdr;
     TreeHdr *hp = d.hdr() + t;
-    const cParams *pl = (const cParams *)__builtin_assume_aligned(base, 256);
     const int Dp = (hsx >= 0 && hsx + 1 <= P) ? hsx : 0;  // the chain's leaf, if the header agrees
 
     if (wv == 1) {
         // ======== wave 1: CTree::back_propagate (cnode.cpp:415-450) over the chain ========
         int8v hv = sload8(hp);  // cursor, tot, D, err, mm_min, mm_max, mm_cnt, leaf
         int r_i = sload1(reward + t), v_i = sload1(value + t);
-        int o_lp = sload1(&pl->d.o_lp);
+        arena();
+        const float *lpt = d.lp();
         int4 a4[NCH];
         float2 cw[NCH];
         float pp[NCH], lpv[NCH];
@@ -3565,26 +3614,8 @@ __global__ __launch_bounds__(192) void k_chain3(char *base, const float *policy,
                 }
             }
         };
-        // (lp's offset arrives with the header: the node records go first)
-#pragma unroll
-        for (int c = 0; c < NCH; ++c) {
-            const int i = c * kWave + l;
-            a4[c] = make_int4(0, 0, 0, 0);
-            cw[c] = make_float2(0.f, 0.f);
-            pp[c] = 0.f;
-            if (i <= Dp) {
-                a4[c] = d.A()[nb + i];
-                cw[c] = *(const float2 *)&d.C()[nb + i];
-                pp[c] = d.PP()[nb + i];
-            }
-        }
-        asm volatile("s_waitcnt lgkmcnt(0)" : "+s"(hv), "+s"(r_i), "+s"(v_i), "+s"(o_lp)::"memory");
-        const float *lpt = (const float *)(base + (size_t)(unsigned)o_lp * 256);
-#pragma unroll
-        for (int c = 0; c < NCH; ++c) {
-            const int i = c * kWave + l;
-            lpv[c] = (i <= Dp) ? lpt[Dp - i] : 0.f;
-        }
+        load(Dp, lpt);  // (one round: every address follows from the preloaded arguments)
+        asm volatile("s_waitcnt lgkmcnt(0)" : "+s"(hv), "+s"(r_i), "+s"(v_i)::"memory");
         const float r_in = i2f(r_i), v_in = i2f(v_i);
         const int herr = hv[3], D = hv[2], toth = hv[1], leafh = hv[7];
         if (herr) return;  // (wave 0 reports; no wave takes the barrier on the error paths)
@@ -3713,10 +3744,16 @@ __global__ __launch_bounds__(192) void k_chain3(char *base, const float *policy,
                 for (int k = 0; k < 16; ++k) glds16a(srow + (o + 1024 * k < lst ? o + 1024 * k : lst), sbig + 1024 * k);
             }
         }
-        int8v io8 = sload8((const void *)iop);  // pool, pool_stride, row_bytes, gather_out
-        int8v hv = sload8(hp);                  // cursor, tot, D, err, mm_min, mm_max, mm_cnt, leaf
-        int rv0 = sload1(&d.A()[nb].x), omri = sload1(&pl->g.one_minus_rho), osti = sload1(&pl->d.o_stats);
-        asm volatile("s_waitcnt lgkmcnt(0)" : "+s"(io8), "+s"(hv), "+s"(rv0), "+s"(omri), "+s"(osti) : : "memory");
+        int16v hv = sload16(hp);  // cursor, tot, D, err, mm_min, mm_max, mm_cnt, leaf, tame, root_vis, leaf_y, hot_tag
+        // pool, pool_stride, row_bytes, gather_out, one_minus_rho, o_stats (wave 2's argument line)
+        int16v io8 = sload16((const void *)iop);
+        asm volatile("s_waitcnt lgkmcnt(0)" : "+s"(io8), "+s"(hv) : : "memory");
+        const int omri = io8[8], osti = io8[9];
+        int rv0 = hv[9];
+        if (hv[11] != hv[1]) {  // no valid hot copy: the root's record
+            arena();
+            rv0 = uni(d.A()[nb].x);
+        }
         stamp(ts, 1);
         // (typed as global memory: flat accesses would count against lgkmcnt too)
         const char *pool = (const char *)(const gchar *)u64_of(io8[0], io8[1]);
@@ -3795,15 +3832,14 @@ __global__ __launch_bounds__(192) void k_chain3(char *base, const float *policy,
     }
 
     // ======== wave 0: CTree::expand (cnode.cpp:224-295) of the leaf: one draw ========
-    int16v hv = sload16(hp);  // cursor, tot, D, err, mm_min, mm_max, mm_cnt, leaf, tame, nxt[0 .. 6]
-    int root_vis0 = sload1(&d.A()[nb].x);
+    // cursor, tot, D, err, mm_min, mm_max, mm_cnt, leaf, tame, root_vis, leaf_y, hot_tag, nxt[0 .. 3]
+    int16v hv = sload16(hp);
+    // idx_x, idy, act and the handle's constants (wave 0's argument line: ChainIO, ChainK)
+    int16v kv = sload16((const char *)iop + offsetof(ChainIO, idx_x));
     int r_i = sload1(reward + t), v_i = sload1(value + t);
-    int4v lb = sload4(&d.Bn()[nb + Dp]);
-    int4v io_xy = sload4((const char *)iop + offsetof(ChainIO, idx_x));  // idx_x, idy
-    int2v io_a = sload2((const char *)iop + offsetof(ChainIO, act));
-    int omri = sload1(&pl->g.one_minus_rho), gWi = sload1(&pl->g.W), oRi = sload1(&pl->d.o_R);
     const float pol = policy[(size_t)t * A + (l < A ? l : 0)];
     const float bet = beta[(size_t)t * A + (l < A ? l : 0)];
+    arena();
     // This launch's record stores, one per lane, from addresses held in registers: lane 0 the child's
     // C, lane 1 the leaf's Bn, lane 2 the child's A, lane 3 the child's Bn (16 bytes each), and the
     // dwords of lane 0 the child's PP, lanes 1-3 idx_x / idy / act.  The node addresses follow from
@@ -3817,23 +3853,38 @@ __global__ __launch_bounds__(192) void k_chain3(char *base, const float *policy,
     uintptr_t p4 = abase + (size_t)d.o_PP * 256 + (nb + (size_t)Dp + 1) * 4;
     asm volatile("" : "+v"(p16), "+v"(p4));
     asm volatile("s_waitcnt lgkmcnt(0)"
-                 : "+s"(hv), "+s"(root_vis0), "+s"(r_i), "+s"(v_i), "+s"(lb), "+s"(io_xy), "+s"(io_a), "+s"(omri),
-                   "+s"(gWi), "+s"(oRi)
+                 : "+s"(hv), "+s"(kv), "+s"(r_i), "+s"(v_i)
                  :
                  : "memory");
+    // The root's visit count and the leaf's Bn.y: the header's copy when the previous launch left a
+    // valid one (k_prepare, k_chain3), else the records (one more round trip: the first fused launch
+    // after a host-path step, or after any other kernel wrote the header)
+    int root_vis0 = hv[9], leaf_by = hv[10];
+    if (hv[11] != hv[1]) {
+        root_vis0 = uni(d.A()[nb].x);
+        leaf_by = uni(d.Bn()[nb + Dp].y);
+    }
     // The next expansion's engine words (the header's nxt), read now for select_walk's fast case --
     // one word per level below the root (its first level is forced while it has one visit): they
     // land while the distribution is built.  The exact case re-reads them after the barrier.
-    const int gW = gWi;
-    const unsigned *Rt = (const unsigned *)(base + (size_t)(unsigned)oRi * 256) + (size_t)t * gW;
+    constexpr int kK0 = (int)((offsetof(ChainIO, k) - offsetof(ChainIO, idx_x)) / 4);  // ChainK's first dword in kv
+    static_assert(kK0 == 6 && offsetof(ChainK, o_sq) == 32, "wave 0's argument line");
+    const int omri = kv[kK0], gW = kv[kK0 + 1];
+    d.o_R = (unsigned)kv[kK0 + 2];
+    d.o_err = (unsigned)kv[kK0 + 3];
+    d.o_D = (unsigned)kv[kK0 + 4];
+    d.o_stats = (unsigned)kv[kK0 + 5];
+    const float gdelta = i2f(kv[kK0 + 6]);
+    d.o_pb = (unsigned)kv[kK0 + 7];
+    d.o_sq = (unsigned)kv[kK0 + 8];
+    const unsigned *Rt = d.R() + (size_t)t * gW;
     const int dA = (A >= 2) ? 2 : 0;
     const int words_fast = SEL ? (hv[2] + 1) - ((root_vis0 + 1 <= 1) ? 1 : 0) : 0;
     const int wi = hv[0] + dA + words_fast + l;
     const unsigned w_fast = Rt[(wi >= 0 && wi < gW) ? wi : 0];
     const float r_in = i2f(r_i), v_in = i2f(v_i);
-    int *const idx_x = (int *)(gchar *)u64_of(io_xy[0], io_xy[1]), *const idy = (int *)(gchar *)u64_of(io_xy[2], io_xy[3]);
-    int *const act = (int *)(gchar *)u64_of(io_a[0], io_a[1]);
-    int4 leaf_b = make_int4(lb.x, lb.y, lb.z, lb.w);
+    int *const idx_x = (int *)(gchar *)u64_of(kv[0], kv[1]), *const idy = (int *)(gchar *)u64_of(kv[2], kv[3]);
+    int *const act = (int *)(gchar *)u64_of(kv[4], kv[5]);
     TreeHdr h;
     h.cursor = hv[0];
     h.tot = hv[1];
@@ -3841,9 +3892,8 @@ __global__ __launch_bounds__(192) void k_chain3(char *base, const float *policy,
     h.err = hv[3];
     h.leaf = hv[7];
     h.tame = hv[8];
-    h.nxt[0] = (unsigned)hv[9];
-    h.nxt[1] = (unsigned)hv[10];
-    d.o_err = pl->d.o_err;
+    h.nxt[0] = (unsigned)hv[12];
+    h.nxt[1] = (unsigned)hv[13];
     if (h.err) {  // a dead tree stays dead and re-reports its error
         if (l == 0) {
             if (SEL) {
@@ -3870,7 +3920,7 @@ __global__ __launch_bounds__(192) void k_chain3(char *base, const float *policy,
             return;
         }
         // out of sequence: the header's leaf (waited for here: no wait for it on the path in sequence)
-        leaf_b = uni4(d.Bn()[nb + D]);
+        leaf_by = uni(d.Bn()[nb + D].y);
         p16 += (long long)(D - Dp) * 16;
         p4 += (long long)(D - Dp) * 4;
     }
@@ -3894,10 +3944,10 @@ __global__ __launch_bounds__(192) void k_chain3(char *base, const float *policy,
     const bool tbl = SEL && root_vis0 >= PS;
     const bool any_err = errp != 0 || tbl;
     const bool tame0 = h.tame && tame_val(v_in) && tame_val(r_in);
-    const int md = md_of(leaf_b.y) < 0 ? 0 : md_of(leaf_b.y);
+    const int md = md_of(leaf_by) < 0 ? 0 : md_of(leaf_by);
     // the records' words by lane (above); the drawn words -- lane 2's prior, lane 3's action and
     // act[t] -- are set after the draw
-    int leaf_y = pack_y(1, act_of(leaf_b.y), md), idx_v = any_err ? 0 : hsx;  // (idx_x: the expanded leaf's)
+    int leaf_y = pack_y(1, act_of(leaf_by), md), idx_v = any_err ? 0 : hsx;  // (idx_x: the expanded leaf's)
     asm volatile("" : "+s"(leaf_y), "+s"(idx_v));
     int4v d16 = {l == 1 ? c : 0, l == 1 ? leaf_y : 0, l == 1 ? f2i(v_in) : 0, l == 1 ? hsx : (l == 3 ? -1 : 0)};
     int d4 = (l == 0) ? f2i(v_in) : t;
@@ -3961,7 +4011,6 @@ __global__ __launch_bounds__(192) void k_chain3(char *base, const float *policy,
     if (SEL && l == 3) st_lane4(p4, any_err ? 0 : a);
     if (!err1 && leaf == 0) {  // (readbacks: root children)
         const float pol_a = rlf(pol, a), bet_a = rlf(bet, a);
-        d.o_D = pl->d.o_D;
         if (l == 0) d.D()[nb + c] = make_float4(pol_a, bet_a, bh, 0.f);
     }
     stamp(ts, 3);
@@ -3982,15 +4031,12 @@ __global__ __launch_bounds__(192) void k_chain3(char *base, const float *policy,
         sA[c] = make_int4(0, f2i(prior), f2i(0.0f), f2i(0.0f));
         wait_lds();
         const int root_visit = uni(sA[0].x);
-        const float gdelta = pl->g.delta;
         const bool mm_on = mm_cnt > 0;
         float den = 0.f;
         if (mm_on) {
             const float delta = mx - mn;
             den = (gdelta < delta) ? delta : gdelta;  // std::max(delta_lb, delta)
         }
-        d.o_pb = pl->d.o_pb;
-        d.o_sq = pl->d.o_sq;
         const float *pbt = d.pb();
         const double *sqt = d.sq();
         for (int i0 = 0; i0 <= Ds; i0 += kWave) {
@@ -4025,6 +4071,11 @@ __global__ __launch_bounds__(192) void k_chain3(char *base, const float *policy,
         hp->mm_cnt = mm_cnt;  // (mm_min / mm_max: wave 1)
         hp->tame = tame;
         hp->leaf = (err || !SEL) ? h.leaf : c;
+        // the hot copy for the next launch: wave 1 adds this back-propagation's visit to the root, and
+        // the new leaf is the child created above (its Bn.y as stored there)
+        hp->root_vis = root_vis0 + 1;
+        hp->leaf_y = pack_y(0, a, -1);
+        hp->hot_tag = (err || !SEL) ? 0 : c + 1;
     }
     if constexpr (!SEL) {
         // the fused readback (mz_expand_backup_readback, include/mzdriver.h): the search's outputs
@@ -4037,9 +4088,8 @@ __global__ __launch_bounds__(192) void k_chain3(char *base, const float *policy,
         if (rbd) {
             const int4 rbn = err ? make_int4(0, 0, 0, 0) : uni4(d.Bn()[nb]);
             const int nc = nc_of(rbn.y), fc = rbn.x;
-            d.o_D = pl->d.o_D;
-            const int md = md_of(leaf_b.y) < 0 ? 0 : md_of(leaf_b.y);
-            const int4 leaf_new = make_int4(c, pack_y(1, act_of(leaf_b.y), md), f2i(v_in), hsx);
+            const int md = md_of(leaf_by) < 0 ? 0 : md_of(leaf_by);
+            const int4 leaf_new = make_int4(c, pack_y(1, act_of(leaf_by), md), f2i(v_in), hsx);
             int4 ca = make_int4(0, 0, 0, 0), cb = ca;
             float4 cd = make_float4(0.f, 0.f, 0.f, 0.f);
             if (l < nc) {
@@ -4054,7 +4104,6 @@ __global__ __launch_bounds__(192) void k_chain3(char *base, const float *policy,
     }
     stamp(ts, 6);
     if (MZ_STAMPS && l >= MZ_S_CYC_HEADER && l < MZ_S_COUNT) {
-        d.o_stats = pl->d.o_stats;
         long long *st = d.stats() + (size_t)t * MZ_S_COUNT;
         long long add = 0;
         switch (l) {
@@ -5439,6 +5488,7 @@ __global__ __launch_bounds__(kTreeWavesN<NC> * 64) void k_tree(char *base, const
                         hp->mm_max = mx2;
                         hp->mm_cnt = cnt2;
                         hp->leaf = x;
+                        hp->hot_tag = 0;  // (K = 1 launches only: never valid on these trees)
                     }
                 }
             }
@@ -6324,6 +6374,7 @@ __global__ __launch_bounds__(kTreeWavesN<NC> * 64) void k_tree(char *base, const
             hp->mm_cnt = mm_cnt;
             hp->tame = h.tame;
             hp->leaf = (err || !SEL) ? h.leaf : x;
+            hp->hot_tag = 0;  // (K = 1 launches only: never valid on these trees)
         }
     }
     if constexpr (!SEL) {
@@ -6610,6 +6661,7 @@ struct mz_batch {
     int nc = 0;                // k_step layout class (0 = layout from Geo)
     int chain_nc = -1;         // k_chain node class for K = 1 trees (-1: k_step for every launch)
     int chain3_nc = 0;         // k_chain3 node class (64 .. 1024) for K = 1 trees, 0: k_chain / k_step
+    ChainK chain_k{};          // k_chain3's copy of the Params fields its waves read (mz_create)
     int tree_nc = -1;          // k_tree node class for 2 <= K <= 64 trees (-1: k_step)
     bool hbm = false;          // the pool's LDS image exceeds a CU's LDS: every step launch is k_hbm
     bool seed_ref = false;     // holds a reference on its device's seeding table (seed_table)
@@ -6974,7 +7026,8 @@ void launch_chain3_row(mz_batch *b, const StepArgs &a) {
     const Geo &g = b->geo;
     const Dev &dv = b->dev;
     // (the first 14 argument dwords, through the discount, arrive preloaded in SGPRs)
-    const ChainIO io{a.pool, a.pool_stride, a.row_bytes, a.gather_out, a.idx_x, a.idy, a.act};
+    const ChainIO io{a.pool, a.pool_stride, a.row_bytes, a.gather_out, b->chain_k.one_minus_rho, b->chain_k.o_stats,
+                     {0, 0, 0, 0, 0, 0}, a.idx_x, a.idy, a.act, b->chain_k};
     // ROW 1, 2: the row size (16-byte units, <= 1024) rides in the preloaded ppk, the leaf's slot in
     // the first argument past the preloaded ones
     const bool pre = ROW == 1 || ROW == 2;
@@ -7562,17 +7615,17 @@ int mz_create(int B, int N, int A, int K, int S, float delta_lb, uint32_t seed, 
     {
         ArenaPlan plan;
         plan.ptr(&b->prm, 1);
+        plan.dev<TreeHdr>(d.o_hdr, (size_t)B);
+        plan.dev<float>(d.o_lp, (size_t)b->PS + 1 + kWave);
         plan.dev<int4>(d.o_A, nodes);
         plan.dev<int>(d.o_Par, nodes);
         plan.dev<int4>(d.o_Bn, nodes);
         plan.dev<float>(d.o_Q, nodes);
         plan.dev<float>(d.o_PP, nodes);
         plan.dev<float4>(d.o_C, nodes);
-        plan.dev<TreeHdr>(d.o_hdr, (size_t)B);
         plan.dev<long long>(d.o_stats, (size_t)B * MZ_S_COUNT);
         plan.dev<int>(d.o_err, 1);
         plan.dev<unsigned>(d.o_seed, 1);
-        plan.dev<float>(d.o_lp, (size_t)b->PS + 1 + kWave);
         plan.dev<float>(d.o_T, (size_t)g.TT + 4 * kWave);
         plan.dev<float>(d.o_pb, (size_t)b->PS + kWave);
         plan.dev<double>(d.o_sq, (size_t)b->PS + kWave);
@@ -7620,6 +7673,14 @@ int mz_create(int B, int N, int A, int K, int S, float delta_lb, uint32_t seed, 
                    &seed_cp, &seed_cp_n);
     b->seed_ref = seed_cp != nullptr;
     const Params host_params{b->geo, b->dev, seed_cp, seed_cp_n};
+    // k_chain3 takes these as launch arguments: fixed from here on, as the Params block they mirror
+    b->chain_k = ChainK{g.one_minus_rho, g.W, d.o_R, d.o_err, d.o_D, d.o_stats, g.delta, d.o_pb, d.o_sq, 0};
+    assert(b->chain_k.one_minus_rho == host_params.g.one_minus_rho && b->chain_k.W == host_params.g.W &&
+           b->chain_k.o_R == host_params.d.o_R && b->chain_k.o_err == host_params.d.o_err &&
+           b->chain_k.o_D == host_params.d.o_D && b->chain_k.o_stats == host_params.d.o_stats &&
+           b->chain_k.delta == host_params.g.delta && b->chain_k.o_pb == host_params.d.o_pb &&
+           b->chain_k.o_sq == host_params.d.o_sq && host_params.d.o_hdr == kArenaHdr &&
+           host_params.d.o_lp == arena_lp((unsigned)B));
     {
         // one launch on the device's init stream, waited for here (the handle's stream is bound later)
         hipStream_t is = init_stream(b->device);
