@@ -53,8 +53,11 @@ def needs_build(lib: str = LIB) -> bool:
     if not os.path.exists(lib):
         return True
     t = os.path.getmtime(lib)
-    deps = [*SRCS, os.path.join(HERE, "csrc", "mz_internal.h"), os.path.join(HERE, "csrc", "mt_seed.inc"), os.path.join(HERE, "csrc", "mzhbm.inc"), os.path.join(ROOT, "include", "mzmcts.h"),
-            os.path.join(ROOT, "include", "mzdriver.h"), os.path.join(ROOT, "include", "mzconsume.h"), __file__]
+    # every source and everything they include under csrc/, by pattern: a new part is a dependency
+    csrc = os.path.join(HERE, "csrc")
+    deps = [os.path.join(csrc, f) for f in sorted(os.listdir(csrc)) if f.endswith((".hip", ".inc", ".h"))]
+    deps += [os.path.join(ROOT, "include", h) for h in ("mzmcts.h", "mzdriver.h", "mzconsume.h")]
+    deps.append(__file__)
     return any(os.path.getmtime(p) > t for p in deps)
 
 

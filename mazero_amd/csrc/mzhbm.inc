@@ -22,12 +22,9 @@
 // to the LDS kernels and to the reference.
 // ------------------------------------------------------------------------------------------------
 
-#ifndef MZ_HBM_WAVES  // (A/B builds)
-#define MZ_HBM_WAVES 8
-#endif
 // eight waves: the expansion on wave 0, the path's nodes dealt over the other seven (one node each
 // up to seven levels), the min/max pass over all eight
-constexpr int kHbmWaves = MZ_HBM_WAVES;
+constexpr int kHbmWaves = 8;
 
 // The bootstrap values of path levels [lo, hi] (chunk of <= 64 levels topped by `carry` at level hi)
 // and, per lane, the path node of level lev = hi - 63 + l: its record and the (already updated)

@@ -1369,12 +1369,6 @@ __global__ __launch_bounds__(256) void k_prepare(const Params *__restrict__ prm,
             }
         }
     } else
-#if defined(MZ_ABL_NOSEED)  // ablation (timing experiments only): no seeding chain
-    if (tid < kWave) {
-        const unsigned x = d.seed()[0] * 2333u + (unsigned)(g.root_offset + t);
-        for (int i = tid; i < kMtN; i += kWave) mt[i] = x + (unsigned)i;
-    }
-#elif !defined(MZ_SEED_LOOP)
     if (tid < kWave) {
         // std::mt19937::seed (sequential by definition) on the scalar unit: 4 SALU operations per
         // word, word i into lane i % 64 of VGPR i / 64 (mt_seed.inc, scripts/gen_mt_seed.py), then
@@ -1399,23 +1393,10 @@ __global__ __launch_bounds__(256) void k_prepare(const Params *__restrict__ prm,
         mt[512 + l] = (unsigned)v8;
         if (576 + l < kMtN) mt[576 + l] = (unsigned)v9;
     }
-#else
-    if (tid == 0) {  // std::mt19937::seed: sequential by definition
-        unsigned x = d.seed()[0] * 2333u + (unsigned)(g.root_offset + t);
-        mt[0] = x;
-        for (int i = 1; i < kMtN; ++i) {
-            x = 1812433253u * (x ^ (x >> 30)) + (unsigned)i;
-            mt[i] = x;
-        }
-    }
-#endif
     // (the twist exchanges LDS data only: barriers that leave the tempered words' global stores in
     // flight instead of draining them at every phase)
     lds_barrier();
     int nb = g.W / kMtN;
-#ifdef MZ_ABL_NOTWIST  // ablation (timing experiments only): no twist / tempering
-    nb = 0;
-#endif
     // One twist per 624-word block (std::mt19937::_M_gen_rand), one barrier each: thread k < 227
     // computes the three words k, k + 227, k + 454 of the new state in registers.  Word k uses old
     // words only; word k + 227 uses new word k (its x[k + 227 - 227]); word k + 454 uses new word
@@ -1683,9 +1664,6 @@ __device__ __forceinline__ void backup(const Geo &g, const Dev &d, Lds &s, int t
     const int l = lane_id();
     const unsigned long long b0 = (MZ_STAMPS != 0) ? __builtin_amdgcn_s_memtime() : 0ull;
     unsigned long long b1 = 0, bw = 0;
-#ifdef MZ_PROBE5
-    unsigned long long pre5 = 0;
-#endif
     // bootstrap values (cnode.cpp:424,448): b_{i-1} = reward_i + discount * b_i from b_D = value,
     // one f32 multiply and one add per level, in the reference's order, in chunks of up to 63
     // levels (boot_dpp): lane j of a chunk topped by level hi holds level hi - 63 + j.
@@ -1704,18 +1682,7 @@ __device__ __forceinline__ void backup(const Geo &g, const Dev &d, Lds &s, int t
             }
             float b = (l == 63) ? carry : 0.f;
             float tmp = (l == 62) ? disc * carry : 0.f;
-#ifdef MZ_PROBE5  // diagnostic: everything outstanding drained before the chain itself
-            {
-                unsigned long long q;
-                asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n s_memtime %0\n s_waitcnt lgkmcnt(0)" : "=s"(q)::"memory");
-                if (hi == D) pre5 = q;
-            }
-#endif
-            int steps = nl;
-#ifdef MZ_ABL_NOBOOT  // ablation (timing experiments only): no recurrence
-            steps = 0;
-#endif
-            boot_dpp(b, tmp, dv, rn, steps);
+            boot_dpp(b, tmp, dv, rn, nl);
             if (lev >= lo && lev <= hi) s.boot[lev] = b;
             if (lo == 0) break;
             carry = rlf(b, 63 - nl);  // level lo, the next chunk's top
@@ -1855,9 +1822,6 @@ __device__ __forceinline__ void backup(const Geo &g, const Dev &d, Lds &s, int t
         wait_lds();
         const unsigned long long b2 = __builtin_amdgcn_s_memtime();
         stl[MZ_S_CYC_BAK_BOOT] += (long long)(b1 - b0);
-#ifdef MZ_PROBE5
-        stl[MZ_S_CYC_MINMAX] += (long long)(pre5 - b0);  // entry -> chain start (all drained)
-#endif
         stl[MZ_S_CYC_BAK_WAIT] += (long long)bw;
         stl[MZ_S_CYC_BAK_NODES] += (long long)(b2 - b1 - bw);
     }
@@ -1986,9 +1950,6 @@ __device__ __forceinline__ void walk_precomputed(const Geo &g, const Dev &d, Lds
                             int nint_pre) {
     const int l = lane_id();
     long long scored = 0;
-#ifdef MZ_PROBE3
-    unsigned long long q0 = __builtin_amdgcn_s_memtime(), q1 = 0, q2 = 0, q3 = 0;
-#endif
     // (1) internal nodes (children count > 0) in s.il: compacted by the expanding wave while it
     // waited for the back-propagation (nint_pre >= 0), else here
     constexpr int kNxtLeaf = -1, kNxtSlow = -2;
@@ -1997,9 +1958,6 @@ __device__ __forceinline__ void walk_precomputed(const Geo &g, const Dev &d, Lds
     int nint = nint_pre;
     if (nint < 0) nint = compact_internal(s, tot);
     wait_lds();
-#ifdef MZ_PROBE3
-    q1 = __builtin_amdgcn_s_memtime();
-#endif
     // (2) select_child's tie list of every internal node (cnode.cpp:355-370), one lane per node,
     // over its children's scores (value_scores): the reference's sequential arg-max with epsilon
     // ties.  A one-child list (the usual case) is stored as the next node; other lists go to the
@@ -2045,9 +2003,6 @@ __device__ __forceinline__ void walk_precomputed(const Geo &g, const Dev &d, Lds
         }
     }
     wait_lds();
-#ifdef MZ_PROBE3
-    q2 = __builtin_amdgcn_s_memtime();
-#endif
     // (3) the walk: one LDS read per level (the next node), one engine word per level; the
     // exact record only for ties, empty lists and table errors.  Level i's node goes to lane i of
     // px (LDS beyond 64 levels).
@@ -2109,10 +2064,6 @@ __device__ __forceinline__ void walk_precomputed(const Geo &g, const Dev &d, Lds
             if (v >= 0) ++cursor;
         }
     }
-#ifdef MZ_PROBE3
-    wait_lds();
-    const unsigned long long q2b = __builtin_amdgcn_s_memtime();
-#endif
     if (cursor > g.W) err |= kErrRng;  // a consumed word beyond the stream (select_word's check)
     if (D == 0) err |= kErrRoot;
     wait_lds();
@@ -2143,22 +2094,12 @@ __device__ __forceinline__ void walk_precomputed(const Geo &g, const Dev &d, Lds
     stl[MZ_S_SELECTS] += 1;
     stl[MZ_S_PATH_EDGES] += D;
     stl[MZ_S_SCORED] += scored;
-#ifdef MZ_PROBE3
-    q3 = __builtin_amdgcn_s_memtime();
-    stl[MZ_S_CYC_W1_ROUND1] += (long long)(q1 - q0);  // compaction
-    stl[MZ_S_CYC_W1_STAGE2] += (long long)(q2 - q1);  // tie lists
-    stl[MZ_S_CYC_W1_BACKUP] += (long long)(q3 - q2);  // walk + path
-    stl[MZ_S_CYC_W1_SYNC] += (long long)(q2b - q2);  // walk loop only
-#endif
 }
 
 // General trees, large pools: level by level, each level's children scored on the fly.
 __device__ __forceinline__ void walk_levels(const Geo &g, const Dev &d, Lds &s, int t, int tot, TreeHdr &h, int lds_base, unsigned rw0, unsigned rw1,
                             int &err, int &out_idx, int &out_act, long long *stl, float disc, int cursor0, int wbase) {
     const int l = lane_id();
-#ifdef MZ_PROBE3
-    const unsigned long long q0 = __builtin_amdgcn_s_memtime();
-#endif
     // General trees: level by level, select_child (cnode.cpp:337-379) scored on the fly, lane j
     // for child j, with ucb_score's arithmetic (cnode.cpp:297-335).  The reference's sequential
     // arg-max with epsilon ties is the closed form [r] + {i > r : s_i >= M - eps} (M the maximum,
@@ -2249,9 +2190,6 @@ __device__ __forceinline__ void walk_levels(const Geo &g, const Dev &d, Lds &s, 
     }
     if (D == 0) err |= kErrRoot;
     wait_lds();
-#ifdef MZ_PROBE3
-    const unsigned long long q1 = __builtin_amdgcn_s_memtime();
-#endif
     // the path {node, visit at selection} for the next back-propagation and the outputs, by the
     // whole wave
     int2 *gp = d.path() + (size_t)t * g.PS;
@@ -2274,13 +2212,6 @@ __device__ __forceinline__ void walk_levels(const Geo &g, const Dev &d, Lds &s, 
     stl[MZ_S_SELECTS] += 1;
     stl[MZ_S_PATH_EDGES] += D;
     stl[MZ_S_SCORED] += nscored;
-#ifdef MZ_PROBE3
-    const unsigned long long q2 = __builtin_amdgcn_s_memtime();
-    stl[MZ_S_CYC_W1_ROUND1] += 0;
-    stl[MZ_S_CYC_W1_STAGE2] += 0;
-    stl[MZ_S_CYC_W1_BACKUP] += (long long)(q2 - q0);  // walk + path
-    stl[MZ_S_CYC_W1_SYNC] += (long long)(q1 - q0);    // walk loop only
-#endif
 }
 
 // --------------------------------------------------------------------------------------------
@@ -2373,13 +2304,6 @@ __global__ __launch_bounds__(128) void k_step(char *base, int P, int PS, int BA,
                                               int hsx, float discount,
                                               int fast_ok, const char *pool, long long pool_stride, long long row_bytes,
                                               char *gather_out, int *idx_x, int *idy, int *act) {
-#ifdef MZ_PROBE2
-    unsigned long long pt0;
-    asm volatile("s_memtime %0\n s_waitcnt lgkmcnt(0)" : "=s"(pt0)::"memory");
-#endif
-#ifdef MZ_ABL_EMPTY  // ablation (timing experiments only): launch cost of this kernel
-    if (true) return;
-#endif
     // The first 14 argument dwords arrive in SGPRs (kernel-argument preloading): the arena base,
     // the geometry (B | A << 24, path bound | handle K << 17: the host passes exactly the Params
     // block's values) and the four network-output pointers, so every round-1 address is computed
@@ -2441,9 +2365,6 @@ __global__ __launch_bounds__(128) void k_step(char *base, int P, int PS, int BA,
     float *sJbet = JOINT ? (float *)(smem + g.oJbet) : nullptr;
     unsigned char *sJ = JOINT ? (smem + g.oJ) : nullptr;
 
-#ifdef MZ_PROBE
-    unsigned long long pr0 = __builtin_amdgcn_s_memtime(), pr1 = 0, pr2 = 0;
-#endif
     if (wv == 0) {
         if (SEL) {
             if (NC == 0 && g.use_table) {
@@ -2456,9 +2377,6 @@ __global__ __launch_bounds__(128) void k_step(char *base, int P, int PS, int BA,
                     if (i0 + l < 2 * g.PS) glds4((const int *)d.sq() + i0 + l, (int *)s.sq + i0);
             }
         }
-#ifdef MZ_PROBE
-        pr1 = __builtin_amdgcn_s_memtime();
-#endif
         if (EB && JOINT) {
             const size_t ib = (size_t)t * g.NA;
             for (int i0 = 0; i0 < g.NA; i0 += kWave)
@@ -2521,12 +2439,6 @@ __global__ __launch_bounds__(128) void k_step(char *base, int P, int PS, int BA,
         r_in = reward[t];
         v_in = value[t];
     }
-#ifdef MZ_ABL_VEC1  // ablation (timing experiments only): launch + the preloaded-address loads only
-    if (true) {
-        wait_vm();
-        return;
-    }
-#endif
     if constexpr (kLateParams) {
         // Params heads the arena: scalar loads from the preloaded base (the scheduler may issue
         // them earlier; nothing above waits for them)
@@ -2585,9 +2497,6 @@ __global__ __launch_bounds__(128) void k_step(char *base, int P, int PS, int BA,
     // counters written per launch: the algorithmic ones, plus the cycle stamps in diagnostic builds
     constexpr int kStatN = (MZ_STAMPS != 0) ? MZ_S_COUNT : MZ_S_CYC_HEADER;
     const long long st_old = (wv == 0 && l < kStatN) ? st[l] : 0;
-#ifdef MZ_PROBE
-    pr2 = __builtin_amdgcn_s_memtime();
-#endif
     if (wv == 0 && g_pre) {
         // issued last and always exactly four loads (offsets clamped into the row), so the
         // round-1 wait below can leave them in flight: the row is needed only at the very end
@@ -2616,12 +2525,6 @@ __global__ __launch_bounds__(128) void k_step(char *base, int P, int PS, int BA,
     if (wv == 0 && l == 0)
         argcheck_record(1, EB, SEL, t, base, P, PS, BA, pk, K, hsx, discount, pe, ne, d.hdr() + t, h.tot, h.cursor,
                         h.D, h.err, (const unsigned *)__builtin_amdgcn_kernarg_segment_ptr(), reward, value, pool, 0);
-#endif
-#ifdef MZ_ABL_ROUND1  // ablation (timing experiments only): launch + round 1, nothing else
-    if (true) {
-        wait_vm();
-        return;
-    }
 #endif
     if (h.err) {  // a dead tree stays dead (both waves see the same header) and re-reports its error
         if (wv == 0 && l == 0) atomicOr(d.err(), h.err);
@@ -2729,16 +2632,10 @@ __global__ __launch_bounds__(128) void k_step(char *base, int P, int PS, int BA,
         } else {
             // ---- CTree::back_propagate (cnode.cpp:415-450) + the min/max normaliser ----
             stamp(ts, 4);
-#ifndef MZ_ABL_W1SKIP  // ablation (timing experiments only): no back-propagation
             backup(g, d, s, t, h.D, tot, v_in, r_in, a.discount, h, cnt0, n0, nv0, need0, off0, err, stl,
                    (float *)(xst + 2 * MZ_S_COUNT));
-#endif
             stamp(ts, 5);
-#if defined(MZ_PROBE2) || defined(MZ_PROBE3)
-            if (false) {
-#else
             if (MZ_STAMPS && SEL) {
-#endif
                 stl[MZ_S_CYC_W1_ROUND1] += (long long)(ts[1] - ts[0]);
                 stl[MZ_S_CYC_W1_STAGE2] += (long long)(ts[3] - ts[2]);
                 stl[MZ_S_CYC_W1_BACKUP] += (long long)(ts[5] - ts[4]);
@@ -2790,26 +2687,14 @@ __global__ __launch_bounds__(128) void k_step(char *base, int P, int PS, int BA,
     if (!EB || JOINT) wait_vm();  // RNG window (and anything staged) has landed (expand_node waited)
     stamp(ts, 6);
     if (SEL && !err) {
-#ifdef MZ_PROBE3
-        const unsigned long long v0 = __builtin_amdgcn_s_memtime();
-#endif
         // K = 1 chains of a tame tree (TreeHdr::tame) under tame handle constants select without
         // scoring: no score can be NaN or below FLOAT_MIN there (select_walk)
         const bool fast = !JOINT && g.K == 1 && fast_ok && h.tame && fabsf(a.discount) <= 1.0f;
         if (!fast && (g.K == 1 || kWalkPrecomputed<NC>)) value_scores(g, s, h.tot, a.discount, h);
-#ifdef MZ_PROBE3
-        stl[MZ_S_CYC_EXP_CDF] = (long long)(__builtin_amdgcn_s_memtime() - v0);  // value scores
-#endif
         // register RNG window: words h.cursor + [0, 128) (select's words follow the expansion's)
         const unsigned rw0 = fast ? 0u : rng_word_win(s.rng, wbase, h.cursor + l);
         const unsigned rw1 = fast ? 0u : rng_word_win(s.rng, wbase, h.cursor + kWave + l);
         int idx = 0, act = 0;
-#ifdef MZ_PROBE3
-        wait_vm();
-        wait_lds();
-        asm volatile("" ::"v"(rw0), "v"(rw1));
-        stl[MZ_S_CYC_EXP_DRAW] = (long long)(__builtin_amdgcn_s_memtime() - v0);  // up to the walk
-#endif
         select_walk<NC>(g, d, s, t, h.tot, h, wbase, rw0, rw1, err, idx, act, stl, fast, a.discount, nint_pre);
         if (l == 0) {
             a.idx_x[t] = idx;
@@ -2899,24 +2784,6 @@ __global__ __launch_bounds__(128) void k_step(char *base, int P, int PS, int BA,
         if (o + 3072 < grb) *(int4 *)(gdst + o + 3072) = gv3;
     }
     stamp(ts, 9);
-#ifdef MZ_PROBE
-    if (EB && SEL && !err) {
-        stl[MZ_S_CYC_W1_ROUND1] = (long long)(pr0 - ts[0]);   // kernel start -> first loads issued
-        stl[MZ_S_CYC_W1_STAGE2] = (long long)(pr1 - pr0);     // T table issue
-        stl[MZ_S_CYC_W1_BACKUP] = (long long)(pr2 - pr1);     // inputs + header issue
-        stl[MZ_S_CYC_W1_SYNC] = (long long)(ts[1] - pr2);     // wait for round 1
-    }
-#endif
-#ifdef MZ_PROBE2
-    if (EB && SEL && !err) {
-        unsigned long long pt1;
-        asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n s_memtime %0\n s_waitcnt lgkmcnt(0)" : "=s"(pt1)::"memory");
-        stl[MZ_S_CYC_W1_ROUND1] = (long long)(ts[0] - pt0);  // kernel entry -> first stamp
-        stl[MZ_S_CYC_W1_STAGE2] = (long long)(pt1 - pt0);    // whole wave-0 span incl. store drain
-        stl[MZ_S_CYC_W1_BACKUP] = (long long)(pt1 - ts[9]);  // store drain after the last stamp
-        stl[MZ_S_CYC_W1_SYNC] = 0;
-    }
-#endif
     if (MZ_STAMPS && EB && SEL && !err) {
         // wave 0's timeline: header, stage1, stage2, expand, wait for the back-propagation wave,
         // value-set/RNG wait, select(+outputs), gather, epilogue
@@ -4148,32 +4015,23 @@ __global__ __launch_bounds__(192) void k_chain3(char *base, const float *policy,
 // staged record and run before the first.
 // --------------------------------------------------------------------------------------------
 // back-propagation waves of k_tree (waves 1 .. kBkN; wave 0 expands): seven (eight waves, two per
-// SIMD) for pools up to 384 nodes, whose trees hold one workgroup per CU, and for the 1,024-node
-// class, whose LDS (150 KB with seven) holds one workgroup per CU either way; four (five waves) for
-// the 512-node class, whose LDS then still fits two workgroups per CU (3s5z: 512 trees)
-#ifndef MZ_TREE_BK
-#define MZ_TREE_BK 7
-#endif
-#ifndef MZ_TREE_BK1024
-#define MZ_TREE_BK1024 MZ_TREE_BK
-#endif
-#ifndef MZ_TREE_BK512
-#define MZ_TREE_BK512 MZ_TREE_BK
-#endif
+// SIMD) in every class.  Pools up to 384 nodes hold one workgroup per CU, and so does the 1,024-node
+// class (150 KB of LDS); the 512-node class keeps two workgroups per CU with seven by staging slots
+// of 128 entries (kBkCapN; 3s5z: 512 trees)
 // The 1024-node class for searches with S + 1 <= 128 (round 5): 128-entry value-entry slots and
 // the layout below fit ~80 KB, two workgroups per CU (3s5z at K = 10: 512 trees of 1,011 nodes in
 // one round over the 256 CUs instead of two).  A class id of its own, one node above 1024.
 constexpr int kTree1024S = 1025;
 template <int NC>
-constexpr int kBkN = (NC <= 384) ? MZ_TREE_BK : (NC >= 1024 ? MZ_TREE_BK1024 : MZ_TREE_BK512);
+constexpr int kBkN = 7;
 template <int NC>
 constexpr int kTreeWavesN = kBkN<NC> + 1;
 constexpr int kBkCap = 340;  // value entries per staging slot (two per wave): S + 1 <= 340
 static_assert(kBkCap + 2 <= (int)kTableFullPS, "k_tree's prior scores read the full pUCT table");
-// the 512-node class with seven back-propagation waves keeps two workgroups per CU (76 KB of LDS
-// each) with slots of 128 entries (S + 1 <= 128; larger searches take k_step); so does kTree1024S
+// the 512-node class keeps two workgroups per CU (76 KB of LDS each) with slots of 128 entries
+// (S + 1 <= 128; larger searches take k_step); so does kTree1024S
 template <int NC>
-constexpr int kBkCapN = (NC == kTree1024S || (NC == 512 && kBkN<NC> > 4)) ? 128 : kBkCap;
+constexpr int kBkCapN = (NC == kTree1024S || NC == 512) ? 128 : kBkCap;
 // a staging slot's stride in int2 entries: CAP entries plus one of lead-in for the 16-byte DMA from
 // the aligned address below a node's first entry (its entries are 8-byte aligned), and one of
 // tail-out, an even count so that every slot starts 16-byte aligned
@@ -4183,34 +4041,17 @@ constexpr int kBkSlot = CAP + 2;
 // O(pool) / 4 waves).  Measured on one box, k_tree fused launch: 27m K = 5 (1010 nodes) 13.8 us by
 // levels against 14.1 us with tree_select_prep; 3m K = 5 (260 nodes) 10.4 against 11.6 us,
 // 3s5z K = 5 (510 nodes) 12.0 against 12.6 us the other way round.
-#ifndef MZ_LEVELS_FROM  // (experiment builds: the smallest class that walks by levels)
-#define MZ_LEVELS_FROM 1024
-#endif
+constexpr int kLevelsFrom = 1024;  // the smallest class that walks by levels
 template <int NC>
-constexpr bool kTreeLevels = (NC >= MZ_LEVELS_FROM);
-// pb_c of the prior scores from the host table in HBM (one gather per node, L2-resident) instead of
-// the staged per-n factors and a double division per node: the gather's wait leaves the SIMD to the
-// wave that shares it.  Same-box A/B: 3s5z K = 5 10.50 -> 10.38 us, 3m K = 5 unchanged;
-// MZ_PBC_FACTORS builds the factor path for A/B runs
-#ifdef MZ_PBC_FACTORS
-template <int NC>
-constexpr bool kTreePbTable = kTreeLevels<NC>;
-#else
-template <int NC>
-constexpr bool kTreePbTable = true;
-#endif
+constexpr bool kTreeLevels = (NC >= kLevelsFrom);
+// pb_c of the prior scores comes from the host table in HBM (one gather per node, L2-resident), not
+// from staged per-n factors and a double division per node: the gather's wait leaves the SIMD to the
+// wave that shares it.  Same-box A/B: 3s5z K = 5 10.50 -> 10.38 us, 3m K = 5 unchanged.
 // The path nodes' new {value, reward} (sAz): per node where the precomputed walk's tie-list records
 // share the array, per path level in the level-walk classes (their walk knows which child lies on
 // the back-propagated path without a lookup: 8 B per node of LDS saved)
 template <int NC>
 constexpr bool kTreeAzLevel = kTreeLevels<NC>;
-// the value-set scalars staged for every node (MZ_C_STAGE A/B builds) or scalar-loaded per path
-// level (default, round 4; see bk_prestage)
-#ifdef MZ_C_STAGE
-constexpr bool kTreeCStage = true;
-#else
-constexpr bool kTreeCStage = false;
-#endif
 // per back-propagation wave, exchanged at barrier (2): its min/max partial, visited-node count,
 // error word and value-entry counters
 struct BkOut {
@@ -4251,10 +4092,7 @@ struct TreeLayout {
     static constexpr int oPol = oIx + r16(4 * kWave);              // f32 [64] the leaf's policy
     static constexpr int oNxt = oPol + r16(4 * kWave);             // u32 [64] the header's engine words
     static constexpr int oSt = oNxt + r16(4 * kWave);              // i64 [64] the tree's statistics counters
-    static constexpr int oCn = oSt + r16(8 * kWave);               // float4 [NC] staged value-set scalars (kTreeCStage)
-    static constexpr int oPb = oCn + (kTreeCStage ? r16(16 * NC) : 0);  // f32 [PSx] logf((n + c2 + 1)/c2) + c1
-    static constexpr int oSq = oPb + (kTreePbTable<NC> ? 0 : r16(4 * (PSx + kWave)));  // f64 [PSx] sqrt(n)
-    static constexpr int oXB = oSq + (kTreePbTable<NC> ? 0 : r16(8 * (PSx + kWave)));  // BkOut [BK + 1] (index = wave)
+    static constexpr int oXB = oSt + r16(8 * kWave);               // BkOut [BK + 1] (index = wave)
     static constexpr int total = oXB + r16((int)sizeof(BkOut) * (BK + 1));
 };
 int tree_lds_bytes(int nc) {
@@ -4271,7 +4109,7 @@ int tree_lds_bytes(int nc) {
 static_assert(TreeLayout<kTree1024S>::total <= 80 * 1024, "kTree1024S: two workgroups per CU");
 
 // ------------------------------------------------------------------------------------------------
-// k_tree's back-propagation on four waves: path level i belongs to wave 1 + i % 4 (kBk waves).
+// k_tree's back-propagation on kBkN waves: path level i belongs to wave 1 + i % kBkN.
 // A wave stages the value entries of its first two levels before barrier (1), from path records it
 // reads with scalar loads (every entry of the node: stage_regions' need test reads structure records
 // that land only at barrier (1)); a third or later level is staged after the previous one is done.
@@ -4281,80 +4119,17 @@ static_assert(TreeLayout<kTree1024S>::total <= 80 * 1024, "kTree1024S: two workg
 // ------------------------------------------------------------------------------------------------
 
 // The value-set scalars (C: weighted_sum, tot_weight) are read by the back-propagation for its path
-// nodes only.  Default: each back-propagation wave loads its own levels' records with scalar loads
-// (the pre-staged levels' in round 1, from the path records it already holds; later levels when it
+// nodes only: each back-propagation wave loads its own levels' records with scalar loads (the
+// pre-staged levels' in round 1, from the path records it already holds; later levels when it
 // reaches them), instead of a round-1 LDS-DMA of every node's record (16 bytes x the pool per tree
-// and launch, round 3).  MZ_C_STAGE builds the staged variant for A/B runs.
-// (kTreeCStage: defined with the class traits above)
-
-// Round-1 staging of k_tree's node records through registers instead of LDS-DMA (-DMZ_STAGE_VGPR,
-// round-6 experiment): every 16-byte record of two arrays loaded into VGPRs (all loads of a batch
-// issued together), then written to LDS.  Bit-exact; same-box A/B: 3m K = 5 7.27 -> 7.37 us, 3m
-// K = 10 7.44 -> 7.59, 3s5z K = 5 9.99 -> 9.91, 27m K = 5 11.48 -> 11.43 (profiles/round6/ab)
-#ifdef MZ_STAGE_VGPR
-constexpr bool kStageVgpr = true;
-#else
-constexpr bool kStageVgpr = false;
-#endif
-template <int MAXC>
-__device__ __forceinline__ void stage_regs16x2(const int4 *s0, int4 *d0, const int4 *s1, int4 *d1, int n) {
-    typedef int int4x __attribute__((ext_vector_type(4)));
-    typedef const __attribute__((address_space(1))) int4x gi4;
-    const int l = lane_id();
-    for (int b0 = 0; b0 < n; b0 += MAXC * kWave) {
-        int4x v0[MAXC], v1[MAXC];
-#pragma unroll
-        for (int c = 0; c < MAXC; ++c) {
-            const int i = b0 + c * kWave + l;
-            if (i < n) {
-                v0[c] = *((gi4 *)(const void *)s0 + i);
-                v1[c] = *((gi4 *)(const void *)s1 + i);
-            }
-        }
-#pragma unroll
-        for (int c = 0; c < MAXC; ++c) {
-            const int i = b0 + c * kWave + l;
-            if (i < n) {
-                *((int4x *)(void *)d0 + i) = v0[c];
-                *((int4x *)(void *)d1 + i) = v1[c];
-            }
-        }
-    }
-}
-template <int MAXC>
-__device__ __forceinline__ void stage_regs4x3(const float *s0, float *d0, const float *s1, float *d1, const int *s2,
-                                              int *d2, int n) {
-    typedef const __attribute__((address_space(1))) float gf;
-    typedef const __attribute__((address_space(1))) int gi;
-    const int l = lane_id();
-    for (int b0 = 0; b0 < n; b0 += MAXC * kWave) {
-        float v0[MAXC], v1[MAXC];
-        int v2[MAXC];
-#pragma unroll
-        for (int c = 0; c < MAXC; ++c) {
-            const int i = b0 + c * kWave + l;
-            if (i < n) {
-                v0[c] = *((gf *)(const void *)s0 + i);
-                v1[c] = *((gf *)(const void *)s1 + i);
-                v2[c] = *((gi *)(const void *)s2 + i);
-            }
-        }
-#pragma unroll
-        for (int c = 0; c < MAXC; ++c) {
-            const int i = b0 + c * kWave + l;
-            if (i < n) {
-                d0[i] = v0[c];
-                d1[i] = v1[c];
-                d2[i] = v2[c];
-            }
-        }
-    }
-}
+// and launch, round 3).
+// The node records themselves are staged by LDS-DMA: staging them through VGPRs (round 6) measured
+// within noise either way (3m K = 5 7.27 -> 7.37 us, 27m K = 5 11.48 -> 11.43; profiles/round6/ab).
 
 struct BkPre {
     int n0, nv0, n1, nv1;  // the pre-staged levels' nodes and entry counts (nv < 0: not staged)
     int ndma;              // LDS-DMA instructions issued for them (the wave's last ones before barrier (1))
-    float4 c0, c1;         // their value-set scalars (scalar loads; unless kTreeCStage)
+    float4 c0, c1;         // their value-set scalars (scalar loads)
     int sh0, sh1;          // their first entry's place in the slot (int2 units: 16-byte DMA from below it)
 };
 
@@ -4363,11 +4138,7 @@ struct BkPre {
 // scalar instructions the compiler otherwise re-derives them with after barrier (1), on the
 // back-propagation's critical path
 __device__ __forceinline__ void bk_pin_offsets(Dev &d) {
-#ifndef MZ_NO_PIN
     asm volatile("" : "+s"(d.o_V), "+s"(d.o_A), "+s"(d.o_C), "+s"(d.o_Bn), "+s"(d.o_Q));
-#else
-    (void)d;
-#endif
 }
 
 // s_waitcnt vmcnt(n) for a wave-uniform n: all but the wave's n most recent vector-memory operations
@@ -4425,7 +4196,7 @@ __device__ __forceinline__ BkPre bk_prestage(const Dev &d, int t, int P, int E, 
         if (j == 0) r.sh0 = sh;
         else r.sh1 = sh;
         // (scalar loads, counted by lgkmcnt: landed by the first LDS wait after barrier (1))
-        const float4 cw = (kTreeCStage) ? make_float4(0.f, 0.f, 0.f, 0.f) : ldsc4(d.C() + (size_t)t * P + pe.x);
+        const float4 cw = ldsc4(d.C() + (size_t)t * P + pe.x);
         if (j == 0) {
             r.n0 = pe.x;
             r.nv0 = pe.y;
@@ -4463,7 +4234,7 @@ __device__ __forceinline__ void bk_boot(const Lds &s, float *boot, int D, float 
 
 // wave k's path levels k, k + BK, ... (CTree::back_propagate, cnode.cpp:415-450, node by node)
 template <int BK, int CAP, bool AZL>  // AZL: sAz per path level (kTreeAzLevel), else per node
-__device__ __forceinline__ void bk_levels(const Geo &g, const Dev &d, const Lds &s, const float4 *sCn, float2 *sAz,
+__device__ __forceinline__ void bk_levels(const Geo &g, const Dev &d, const Lds &s, float2 *sAz,
                                           const float *boot, int2 *sReg, BkPre pre, int t, int D, float reward,
                                           float disc, int k, int &err, long long &ent_r, long long &ent_w, float &pmn,
                                           float &pmx, unsigned long long *tl = nullptr) {
@@ -4496,8 +4267,7 @@ __device__ __forceinline__ void bk_levels(const Geo &g, const Dev &d, const Lds 
         const int4 b4 = s.B[n];
         const int4 a4r = s.A[n];
         float4 cw;
-        if (kTreeCStage) cw = sCn[n];
-        else if (j == 0 && pre.nv0 >= 0) cw = pre.c0;
+        if (j == 0 && pre.nv0 >= 0) cw = pre.c0;
         else if (j == 1 && pre.nv1 >= 0) cw = pre.c1;
         else cw = ldsc4(d.C() + (size_t)t * g.P + n);  // (a later level)
         const float ppn = s.PP[n];
@@ -4616,69 +4386,24 @@ __device__ __forceinline__ void bk_levels(const Geo &g, const Dev &d, const Lds 
 // Wave 0 then chases next nodes one LDS read per level.
 constexpr int kTreeLeaf = -1, kTreeSlow = -2;
 
-
-
-// Who stages the value-set scalars in round 1: wave 0 (with the path, the flags and the leaf's
-// inputs) or, for the 1024-node class, wave 4.  Same-box A/B: 3m K = 10 9.77 -> 9.64 us with wave 4;
-// the smaller classes measured no gain (3m K = 5) or a loss (3s5z K = 5, 10.47 -> 10.59 us).
 // Who gathers the leaf's row in the precomputed-walk classes: wave 1, after its own copy of the
 // chase (the same reads of the same LDS state), while wave 0 writes the path record, the header
 // and the counters; the level walk (1024-node class) gathers on wave 0.
 template <int NC>
-#ifdef MZ_NO_W1G
-constexpr bool kTreeW1Gather = false;
-#else
 constexpr bool kTreeW1Gather = !kTreeLevels<NC>;
-#endif
 
 // The waves that score every node and resolve the tie lists after barrier (2) (tree_select_prep):
 // four where a pass of four waves covers the pool (<= 256 nodes), every wave of the workgroup in the
 // larger classes, where four waves took two passes of each phase (round 6, same-box A/B against the
-// same build with four, MZ_SEL_W4: 3s5z K = 5 10.08 -> 9.98 us, 3m K = 10 unchanged at 7.60)
+// same build with four: 3s5z K = 5 10.08 -> 9.98 us, 3m K = 10 unchanged at 7.60)
 template <int NC>
-#ifdef MZ_SEL_W4
-constexpr int kSelW = 4;
-#else
 constexpr int kSelW = (NC > 256 && !kTreeLevels<NC>) ? kTreeWavesN<NC> : 4;
-#endif
 
-// Round-6 experiment (-DMZ_HELPER_CDF): the leaf's sampling distribution (discrete_distribution's
-// probabilities and prefix sums, cnode.cpp:243-262) computed before barrier (1) by the last
-// back-propagation role (hardware wave 4, on wave 0's SIMD; its path levels are the deepest and
-// usually absent) while wave 0 waits for its round-1 loads, wave 0 reading the CDF after barrier (1).
-// Bit-exact, but slower in every configuration (same-box A/B against the same build without it:
-// 3m K = 5 7.22 -> 7.57 us, 3m K = 10 7.44 -> 7.60, 3s5z K = 5 9.92 -> 9.98, 27m K = 5
-// 11.43 -> 11.58; profiles/round6/ab): the helper's beta load and distribution delay barrier (1)
-// for every wave, and the expansion it shortens ends before the back-propagation anyway
-#ifdef MZ_HELPER_CDF
-constexpr bool kTreeHelperCdf = true;
-#else
-constexpr bool kTreeHelperCdf = false;
-#endif
-
-// Round-6 experiment (-DMZ_SCORE_WALK): in the precomputed classes, after barrier (2) the four waves
-// score every node (S1) and each chase copy then walks from the root over those scores (score_walk:
-// per level the children's scores in one LDS round trip, the sequential arg-max in closed form by a
-// DPP row max and two ballots) instead of resolving every internal node's tie list (S2) and chasing
-// the resolved outcomes (tree_chase).  Bit-exact (the GPU suite passes on it), but slower: wave 0's
-// stamps at 3m K = 5 put S1 at ~1,400 cycles and S2 at ~1,380, and a walked level at ~950 cycles
-// against ~460 per chased level (its serial chain of LDS round trip, DPP max, readfirstlane, two
-// ballots and readlanes), so S1 + walk ~5,200 against S1 + S2 + chase ~4,600; fused launch
-// 7.26 -> 8.47 us, 3m K = 10 7.50 -> 8.13, 3s5z K = 5 10.10 -> 10.96 (profiles/round6/ab).
-template <int NC>
-#ifdef MZ_SCORE_WALK
-constexpr bool kTreeScoreWalk = !kTreeLevels<NC>;
-#else
-constexpr bool kTreeScoreWalk = false;
-#endif
-
-template <int NC>
-#ifdef MZ_C_W4
-constexpr bool kTreeCW4 = true;
-#else
-constexpr bool kTreeCW4 = kTreeLevels<NC>;
-#endif
-
+// Two round-6 variants were measured, lost and removed (profiles/round6/ab): the leaf's
+// CDF computed before barrier (1) by the last back-propagation role was slower in every configuration
+// (3m K = 5 7.22 -> 7.57 us: it delays barrier (1) for every wave), and a walk from the root over
+// S1's scores in place of S2 and the chase was slower too (3m K = 5 7.26 -> 8.47 us: ~950 cycles per
+// walked level against ~460 per chased one).
 
 // The chase's common levels (wave 0, uniform control flow): while the current outcome v is a child
 // (a one-member list inside the table, tree_select_prep's next node) and the path stays under lim
@@ -4862,31 +4587,8 @@ __device__ __forceinline__ void tree_select_prep(unsigned char *smem, int wv, in
         const float delta = mmx - mmn;
         den = (gdelta < delta) ? delta : gdelta;  // std::max(delta_lb, delta)
     }
-#ifdef MZ_S12_FUSED
-    // (S) one pass (round-5 experiment, MZ_S12_FUSED builds): every internal node scores its own
-    // children inline (ucb_score, cnode.cpp:297-335) and resolves select_child (cnode.cpp:337-379),
-    // with no barrier between the scores and the tie lists; the exact records' list bits go to the
-    // value-entry staging area.  Measured and kept out (same-box A/B, fused launch): 3m K = 5
-    // 7.57 -> 8.65 us, 3m K = 10 7.87 -> 9.71, 3s5z K = 5 10.25 -> 11.57: a lane scores up to eight
-    // children (~25 instructions each, every lane of the wave issuing them) where (S1) scores one
-    // node per lane, which costs more than the barrier it saves.
-    float2 *sRec = (float2 *)(smem + L::oReg);
-    auto score = [&](int c) {
-        const int4 a = sA[c];
-        const int fl = sFl[c];
-        const float2 az = sAz[c];
-        const int vis = a.x + (fl ? 1 : 0);
-        const float val = fl ? az.x : i2f(a.z);
-        const float rw = fl ? az.y : i2f(a.w);
-        float vs = (vis == 0) ? 0.0f : ((rw + disc * val) - sPP[c]);
-        if (mm_on) vs = (vs - mmn) / den;
-        if (vs < 0) vs = 0;
-        if (vs > 1) vs = 1;
-        return sSc[c] + vs;  // prior_score + value_score
-    };
-    if (MZ_STAMPS && tp) tp[0] = __builtin_amdgcn_s_memtime();
-#else
-    float2 *sRec = sAz;
+    // (kept as a lambda on purpose: a direct sSc[c] read below gives the address arithmetic another
+    // shape and reschedules k_tree<64..512>; profiles/prune_split/README.md)
     auto score = [&](int c) { return sSc[c]; };
     for (int n0 = wv * kWave; n0 < ntot; n0 += kSelW<NC> * kWave) {  // (S1)
         const int n = n0 + l;
@@ -4902,7 +4604,6 @@ __device__ __forceinline__ void tree_select_prep(unsigned char *smem, int wv, in
             if (vs < 0) vs = 0;
             if (vs > 1) vs = 1;
             sSc[n] = sSc[n] + vs;  // prior_score + value_score
-            if constexpr (kTreeScoreWalk<NC>) sQ[n] = i2f(vis);  // (score_walk: visits after the back-propagation)
         }
     }
     if (MZ_STAMPS && tp) {
@@ -4910,8 +4611,6 @@ __device__ __forceinline__ void tree_select_prep(unsigned char *smem, int wv, in
         tp[0] = __builtin_amdgcn_s_memtime();
     }
     lds_barrier();  // (3)
-    if constexpr (kTreeScoreWalk<NC>) return;  // (no tie lists: the walk resolves its own levels)
-#endif
     for (int p0 = wv * kWave; p0 < ntot; p0 += kSelW<NC> * kWave) {  // (S2)
         const int p = p0 + l;
         if (p < ntot) {
@@ -4925,7 +4624,6 @@ __device__ __forceinline__ void tree_select_prep(unsigned char *smem, int wv, in
                 float mx = -1000000.0f;  // FLOAT_MIN (utils.h:12)
                 unsigned long long lst = 0ull;
                 int cnt = 0;
-#ifndef MZ_S2_SEQ
                 if (nc <= 8) {
                     // up to eight children: the sequential arg-max in closed form (as the level walk),
                     // the first maximum r and every later child within epsilon of it; {s >= FLOAT_MIN}
@@ -4955,7 +4653,6 @@ __device__ __forceinline__ void tree_select_prep(unsigned char *smem, int wv, in
                     lst = ge;
                     cnt = __builtin_popcount(ge);
                 } else
-#endif
                 for (int i0 = 0; i0 < nc; i0 += 4) {
                     float sc[4];
 #pragma unroll
@@ -4977,7 +4674,7 @@ __device__ __forceinline__ void tree_select_prep(unsigned char *smem, int wv, in
                     nxt[p] = fc + __builtin_ctzll(lst);
                 } else {
                     nxt[p] = kTreeSlow;
-                    sRec[p] = make_float2(i2f((int)(unsigned)(lst & 0xffffffffull)), i2f((int)(unsigned)(lst >> 32)));
+                    sAz[p] = make_float2(i2f((int)(unsigned)(lst & 0xffffffffull)), i2f((int)(unsigned)(lst >> 32)));
                     sQ[p] = i2f(cnt | (terr ? 0x10000 : 0));
                 }
             }
@@ -5006,11 +4703,7 @@ __device__ __forceinline__ void tree_chase(unsigned char *smem, const Dev &d, in
     int2 *sPath = (int2 *)(smem + L::oPath);
     const unsigned *sRng = (const unsigned *)(smem + L::oRng);
     const int *nxt = (const int *)(smem + L::oPar);
-#ifdef MZ_S12_FUSED
-    const float2 *rec = (const float2 *)(smem + L::oReg);  // (tree_select_prep's exact records)
-#else
     const float2 *rec = (const float2 *)(smem + L::oAz);
-#endif
     cursor = uni(cursor);
     int v;
     const unsigned nxb = lds_addr(smem) + L::oPar;
@@ -5034,7 +4727,6 @@ __device__ __forceinline__ void tree_chase(unsigned char *smem, const Dev &d, in
         cursor = uni(cursor);
         if (v < 0) {
             if (v == kTreeLeaf) break;
-#ifndef MZ_SLOW_OLD
             // the exact record: ties (engine word modulo the list size), an empty list (child 0, no
             // word) or a table error.  Everything it reads depends only on x and the cursor, so all
             // of it is one LDS round trip; the k-th listed child is one ballot (mbcnt rank)
@@ -5070,35 +4762,6 @@ __device__ __forceinline__ void tree_chase(unsigned char *smem, const Dev &d, in
                 ++cursor;
             }
             v = uni(uni(bx) + ci);
-#else
-            // the exact record: ties (engine word modulo the list size), an empty list (child
-            // 0, no word) or a table error
-            const int xfl = uni(f2i(sQ[x]));
-            if (uni(xfl >> 16)) {
-                err |= kErrTable;
-                break;
-            }
-            const int cnt = uni(xfl & 0xffff);
-            int ci = 0;
-            if (cnt > 0) {
-                const float2 rb = rec[x];
-                unsigned long long lst = ((unsigned long long)(unsigned)uni(f2i(rb.y)) << 32) |
-                                         (unsigned)uni(f2i(rb.x));
-                if (cursor >= gW) {
-                    err |= kErrRng;
-                    break;
-                }
-                if (cnt > 1) {
-                    const int o = cursor - wbase + wsh;
-                    const unsigned w = (o >= wsh && o < kRngWin) ? (unsigned)uni((int)sRng[o])
-                                                               : (unsigned)uni((int)d.R()[(size_t)t * gW + cursor]);
-                    for (int k = uni((int)(w % (unsigned)cnt)); k > 0; --k) lst &= lst - 1ull;
-                }
-                ++cursor;
-                ci = uni(__builtin_ctzll(lst));
-            }
-            v = uni(uni(sB[x].x) + ci);
-#endif
         }
         if (Dn + 1 >= PS) {
             err |= kErrPath;
@@ -5114,113 +4777,6 @@ __device__ __forceinline__ void tree_chase(unsigned char *smem, const Dev &d, in
     }
     if (cursor > gW) err |= kErrRng;  // a consumed word beyond the stream
     if (Dn == 0) err |= kErrRoot;
-}
-
-// select_path (cnode.cpp:381-413) over the scores of tree_select_prep's S1 (sSc: every node's ucb_score
-// under its parent after this back-propagation; sQ: its visits).  The interface and outcomes of
-// tree_chase: per level one LDS round trip for the children's scores, structure records and visits
-// (lane j = child j), the first maximum by a DPP row max (a wave max past 16 children) and
-// select_child's tie list (cnode.cpp:355-370) in closed form, one engine word per non-empty list
-// (gen() % size, cnode.cpp:373-377), the next level's records from the chosen lane.
-template <int NC, bool REC>
-__device__ __forceinline__ void score_walk(unsigned char *smem, const Dev &d, int t, int gW, int wbase, int wsh,
-                                           int PS, int &cursor, int &err, int &Dn, int &x, int &xprev, int &px,
-                                           int &nbw) {
-    using L = TreeLayout<NC>;
-    const int l = lane_id();
-    const int4 *sA = (const int4 *)(smem + L::oA);
-    const int4 *sB = (const int4 *)(smem + L::oB);
-    const float *sSc = (const float *)(smem + L::oPS);
-    const int *sVis = (const int *)(smem + L::oQ);
-    int2 *sPath = (int2 *)(smem + L::oPath);
-    const unsigned *sRng = (const unsigned *)(smem + L::oRng);
-    cursor = uni(cursor);
-    int xv = uni(sA[0].x) + 1;  // the root is on every back-propagated path
-    int xb_x = uni(sB[0].x), xb_y = uni(sB[0].y);
-    x = 0;
-    while (true) {
-        const int nc = uni(nc_of(xb_y));
-        if (nc == 0) break;  // a leaf
-        const int fc = uni(xb_x);
-        const bool has = l < nc;
-        float sc = -INFINITY;
-        int cbx = 0, cby = 0, cvis = 0;
-        if (has) {
-            sc = sSc[fc + l];
-            const int2 cb = *(const int2 *)&sB[fc + l];
-            cbx = cb.x;
-            cby = cb.y;
-            cvis = sVis[fc + l];
-        }
-        int ci = 0;
-        if (x == 0 && xv <= nc) {
-            ci = xv - 1;  // forced root round-robin (cnode.cpp:398-399): no word
-        } else {
-            const int np = xv - 1;  // total_children_visit_counts = node->visit_count - 1
-            if (np < 0 || np >= PS) {
-                err |= kErrTable;
-                break;
-            }
-            float M;
-            if (nc <= 16) {  // one DPP row holds every child
-                float v = sc;
-                v = fmaxf(v, i2f(dpp<0xB1>(f2i(v))));
-                v = fmaxf(v, i2f(dpp<0x4E>(f2i(v))));
-                v = fmaxf(v, i2f(dpp<0x141>(f2i(v))));
-                v = fmaxf(v, i2f(dpp<0x140>(f2i(v))));
-                M = unif(v);
-            } else {
-                M = unif(wave_max(sc));
-            }
-            unsigned long long lst;
-            if (M > -1000000.0f) {  // FLOAT_MIN (utils.h:12)
-                const unsigned long long first = ballot(has && sc == M);
-                const int r = uni(__builtin_ctzll(first));
-                lst = ballot(has && sc >= M - 0.000001f) & (~0ull << r);
-            } else {
-                lst = ballot(has && sc >= -1000000.0f);
-            }
-            const int cnt = uni(__popcll(lst));
-            if (cnt > 0) {
-                if (cursor >= gW) {
-                    err |= kErrRng;
-                    break;
-                }
-                if (cnt > 1) {  // ties: the engine word modulo the list size picks the listed child
-                    const int o = cursor - wbase + wsh;
-                    const bool inwin = o >= wsh && o < kRngWin;
-                    if (!inwin) ++nbw;  // (MZ_S_RNG_TIE_BEYOND)
-                    const unsigned w = inwin ? (unsigned)uni((int)sRng[o]) : (unsigned)uni((int)d.R()[(size_t)t * gW + cursor]);
-                    for (int k = uni((int)(w % (unsigned)cnt)); k > 0; --k) lst &= lst - 1ull;
-                }
-                ++cursor;
-                ci = uni(__builtin_ctzll(lst));
-            }
-        }
-        if (Dn + 1 >= PS) {
-            err |= kErrPath;
-            break;
-        }
-        xprev = x;
-        x = uni(fc + ci);
-        ++Dn;
-        if (Dn < kWave) px = wl(px, x, Dn);
-        else if (REC && l == 0) sPath[Dn] = make_int2(x, 0);
-        xv = uni(rl(cvis, ci));
-        xb_x = uni(rl(cbx, ci));
-        xb_y = uni(rl(cby, ci));
-    }
-    if (Dn == 0) err |= kErrRoot;
-}
-
-// the precomputed classes' selection from the state tree_select_prep left: score_walk or tree_chase
-template <int NC, bool REC>
-__device__ __forceinline__ void tree_select(unsigned char *smem, const Dev &d, int t, int gW, int wbase, int wsh, int PS,
-                                            int &cursor, int &err, int &Dn, int &x, int &xprev, int &px, int &nbw) {
-    if constexpr (kTreeScoreWalk<NC>)
-        score_walk<NC, REC>(smem, d, t, gW, wbase, wsh, PS, cursor, err, Dn, x, xprev, px, nbw);
-    else
-        tree_chase<NC, REC>(smem, d, t, gW, wbase, wsh, PS, cursor, err, Dn, x, xprev, px, nbw);
 }
 
 template <int NC, bool SEL = true>  // SEL = false: the last expansion of a search (mz_expand_backup)
@@ -5240,11 +4796,7 @@ __global__ __launch_bounds__(kTreeWavesN<NC> * 64) void k_tree(char *base, const
     // the level-walk classes with one workgroup per CU: wave 0 hands the leaf's parent over through
     // LDS (xi[56]: 0 pending, index + 1, or -1 for none) and wave 1 gathers the row, in parallel
     // with wave 0's epilogue
-#ifdef MZ_NO_LVG
-    constexpr bool lvg = false;
-#else
     const bool lvg = SEL && kTreeLevels<NC> && pool != nullptr && (fast_ok & 2) != 0;
-#endif
     const int B = BA & 0xffffff, A = (int)((unsigned)BA >> 24);
     const int pe = pk & 0x1ffff, gK = (int)((unsigned)pk >> 17);
     const int ne = (1ll + (long long)gK * (pe - 1)) < P ? 1 + gK * (pe - 1) : P;  // node bound (launch_step)
@@ -5261,8 +4813,6 @@ __global__ __launch_bounds__(kTreeWavesN<NC> * 64) void k_tree(char *base, const
     int *sFl = (int *)(smem + L::oFl);
     float2 *sAz = (float2 *)(smem + L::oAz);
     int2 *sPath = (int2 *)(smem + L::oPath);
-    float *spb = (float *)(smem + L::oPb);
-    double *ssq = (double *)(smem + L::oSq);
     float *sLp = (float *)(smem + L::oLp);
     unsigned *sRng = (unsigned *)(smem + L::oRng);
     float *xf = (float *)(smem + L::oX);
@@ -5270,15 +4820,14 @@ __global__ __launch_bounds__(kTreeWavesN<NC> * 64) void k_tree(char *base, const
     long long *xl = (long long *)(smem + L::oX + 64);
     const int t = blockIdx.x;
     const int l = threadIdx.x & (kWave - 1);
-    // wave roles: 0 expands, 1 .. 4 back-propagate (2 and 3 also stage).  Five waves on four SIMDs:
-    // one SIMD holds two, so the lightest roles, 3 and 4, get hardware waves 0 and 4 (wave w on SIMD
-    // w % 4); role 4 ends at barrier (2), before the scores and tie lists of roles 0 .. 3
-    // (eight waves: hardware waves w and w + 4 share SIMD w % 4; roles 0 .. 3 -- the expansion, the
-    // root, path levels 1 and 2 -- get one SIMD each, paired with the roles of the deepest levels 6,
-    // 5, 4, 3, which also take the prior-score blocks)
+    // wave roles: 0 expands, 1 .. BK back-propagate (2 and 3 also stage).  Eight waves on four SIMDs:
+    // hardware waves w and w + 4 share SIMD w % 4; roles 0 .. 3 -- the expansion, the root, path
+    // levels 1 and 2 -- get one SIMD each, paired with the roles of the deepest levels 6, 5, 4, 3,
+    // which also take the prior-score blocks
     constexpr int BK = kBkN<NC>;
+    static_assert(BK == 7, "k_tree's role mapping: eight waves, two per SIMD");
     const int hw = (int)(threadIdx.x >> 6);
-    const int wv = uni(BK == 4 ? (hw == 0 ? 3 : (hw == 4 ? 4 : hw - 1)) : (hw < 4 ? hw : BK + 4 - hw));
+    const int wv = uni(hw < 4 ? hw : BK + 4 - hw);
     BkOut *xbo = (BkOut *)(smem + L::oXB);
     const size_t nb = (size_t)t * P;
     unsigned long long ts[10] = {0};
@@ -5294,40 +4843,18 @@ __global__ __launch_bounds__(kTreeWavesN<NC> * 64) void k_tree(char *base, const
         // ======== waves 2 .. kBk: stage the node records (waves 2, 3); back-propagate their path
         // levels; then the prior scores after the back-propagation and the min/max over the visited
         // nodes off the path ========
-        // (the helper role: the leaf's beta, one action per lane, first)
-        const bool cdf_helper = kTreeHelperCdf && wv == BK && A >= 2;
-        float hbet = 0.f;
-        if (cdf_helper && l < A) hbet = beta[(size_t)t * A + l];
         int2 bp0, bp1;
         bk_path_records<BK>(d, t, PS, wv - 1, bp0, bp1);
         const float omr = pl->g.one_minus_rho, gdel = pl->g.delta;  // (issued with the header's loads)
         if constexpr (!kTreeLevels<NC>) bk_pin_offsets(d);  // (the 1024-node class: measured slower)
         const bool al = (P & 3) == 0;  // the tree's 4-byte arrays start 16-byte aligned
-        if (kStageVgpr && wv == 2) {
-            stage_regs16x2<(NC >= 512 ? 4 : NC / kWave)>(d.A() + nb, sA, d.Bn() + nb, sB, ne);
-        } else if (kStageVgpr && wv == 3) {
-            stage_regs4x3<(NC >= 512 ? 8 : NC / kWave)>(d.PP() + nb, sPP, d.Q() + nb, sQ, d.Par() + nb, sPar, ne);
-        } else if (wv == 2) {
+        if (wv == 2) {
             dma_dwords(d.A() + nb, lds_addr(smem) + L::oA, 4 * ne, true);
             dma_dwords(d.Bn() + nb, lds_addr(smem) + L::oB, 4 * ne, true);
         } else if (wv == 3) {
             dma_dwords(d.PP() + nb, lds_addr(smem) + L::oPP, ne, al);
             dma_dwords(d.Q() + nb, lds_addr(smem) + L::oQ, ne, al);
             dma_dwords(d.Par() + nb, lds_addr(smem) + L::oPar, ne, al);
-        } else if (kTreeCStage && kTreeCW4<NC> && wv == 4) {  // wave 4: the value-set scalars (kTreeCW4)
-            for (int i0 = 0; i0 < ne; i0 += kWave)
-                if (i0 + l < ne)
-                    asm volatile("s_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, off" ::"v"(d.C() + nb + i0 + l), "s"(lds_addr(smem) + (unsigned)(L::oCn + 16 * i0)) : "memory", "m0");
-        }
-#ifdef MZ_ABL_LINES  // experiment: MZ_ABL_LINES x 16 extra cache lines in round 1 (value entries, discarded)
-        if (wv == 2) {
-            const int2 *gVt = (const int2 *)(d.base + (size_t)pl->d.o_V * 256) + (size_t)t * P * pl->g.E;
-            for (int k = 0; k < MZ_ABL_LINES; ++k) glds16a((const char *)gVt + 1024 * k + 16 * l, smem + L::oReg + 1024 * k);
-        }
-#endif
-        if (SEL && !kTreePbTable<NC> && wv == 3) {  // the pUCT factors per parent visit count (no gathers)
-            dma_dwords(d.pb(), lds_addr(smem) + L::oPb, PS, true);
-            dma_dwords(d.sq(), lds_addr(smem) + L::oSq, 2 * PS, true);
         }
         const int herr = hp0->err, tot = hp0->tot, D = hp0->D;
         if (herr) {
@@ -5348,7 +4875,6 @@ __global__ __launch_bounds__(kTreeWavesN<NC> * 64) void k_tree(char *base, const
                     if (wv == 2) {
                         glds16a(d.A() + nb + i0 + l, sA + i0);
                         glds16a(d.Bn() + nb + i0 + l, sB + i0);
-                        if (kTreeCStage) glds16a(d.C() + nb + i0 + l, (float4 *)(smem + L::oCn) + i0);  // (wave 0 stages ne)
                     } else if (wv == 3) {
                         glds4a(d.PP() + nb + i0 + l, sPP + i0);
                         glds4a(d.Q() + nb + i0 + l, sQ + i0);
@@ -5358,13 +4884,6 @@ __global__ __launch_bounds__(kTreeWavesN<NC> * 64) void k_tree(char *base, const
         // this wave's path levels' value entries: issued last, in flight across barrier (1)
         const BkPre pre = bk_prestage<BK, kBkCapN<NC>>(d, t, P, g.E, D, wv - 1, bp0, bp1, (int2 *)(smem + L::oReg));
         wait_vm_but(pre.ndma);
-        if (cdf_helper) {
-            // the leaf's CDF for wave 0's draws: cp[a] in oU (oIx: the weights' broadcast scratch, free
-            // until the epilogue)
-            double *hcp = (double *)(smem + L::oU);
-            const double cp = cdf_bcast(hbet, A, (float *)(smem + L::oIx), hcp);
-            hcp[l] = cp;  // (after this wave's own reads of the probabilities there)
-        }
         stamp(ts, 1);
         lds_barrier();  // (1)
         stamp(ts, 2);
@@ -5381,7 +4900,7 @@ __global__ __launch_bounds__(kTreeWavesN<NC> * 64) void k_tree(char *base, const
         int berr = 0;
         long long ber = 0, bew = 0;
         float bmn, bmx;
-        bk_levels<BK, kBkCapN<NC>, kTreeAzLevel<NC>>(g, d, s, (const float4 *)(smem + L::oCn), sAz, boot, (int2 *)(smem + L::oReg), pre, t, D, r_in,
+        bk_levels<BK, kBkCapN<NC>, kTreeAzLevel<NC>>(g, d, s, sAz, boot, (int2 *)(smem + L::oReg), pre, t, D, r_in,
                   discount, wv - 1, berr, ber, bew, bmn, bmx);
         stamp(ts, 3);
         // nodes 1 .. tot-1 in 64-node blocks dealt round-robin over waves 2 .. kBk, the deepest
@@ -5390,7 +4909,6 @@ __global__ __launch_bounds__(kTreeWavesN<NC> * 64) void k_tree(char *base, const
         constexpr int NPW = BK - 1;
         constexpr int NBW = (NC + NPW * kWave - 1) / (NPW * kWave);
         const float *T = d.T();
-        (void)T;
         float pbc[NBW];
         float mn = INFINITY, mx = -INFINITY;
         int cv = 0;
@@ -5406,11 +4924,8 @@ __global__ __launch_bounds__(kTreeWavesN<NC> * 64) void k_tree(char *base, const
                 int v = a.x + (fn ? 1 : 0);
                 if (SEL && np >= 0 && np < PS) {
                     if (v > np) v = np;  // (not in a consistent tree; as the host table's range)
-                    // pb_c (cnode.cpp:313-314): the host-built table for the 1024-node class (its many
-                    // nodes make the double division cost more than the gathers), else from the
-                    // staged per-n factors with the same double arithmetic
-                    if constexpr (kTreePbTable<NC>) pbc[k] = T[np * (np + 1) / 2 + v];
-                    else pbc[k] = (float)((double)spb[np] * (ssq[np] / (double)(v + 1)));
+                    // pb_c (cnode.cpp:313-314) from the host-built table
+                    pbc[k] = T[np * (np + 1) / 2 + v];
                 }
                 if (a.x > 0 && !fn) {
                     const float q = sQ[n];
@@ -5461,7 +4976,7 @@ __global__ __launch_bounds__(kTreeWavesN<NC> * 64) void k_tree(char *base, const
                 const int gW2 = pl->g.W;
                 d.o_R = pl->d.o_R;
                 int cur = uni(xi[58]), Dn = 0, x = 0, xprev = 0, px = 0, e = 0, nbw = 0;
-                tree_select<NC, false>(smem, d, t, gW2, uni(xi[62]), uni(xi[59]), PS, cur, e, Dn, x, xprev, px, nbw);
+                tree_chase<NC, false>(smem, d, t, gW2, uni(xi[62]), uni(xi[59]), PS, cur, e, Dn, x, xprev, px, nbw);
                 if (!e) {
                     TreeHdr *hp = d.hdr() + t;
                     const int wb = uni(xi[62]), ws = uni(xi[59]);
@@ -5549,7 +5064,7 @@ __global__ __launch_bounds__(kTreeWavesN<NC> * 64) void k_tree(char *base, const
         int err = 0;
         long long ent_r = 0, ent_w = 0;
         float pmn, pmx;
-        bk_levels<BK, kBkCapN<NC>, kTreeAzLevel<NC>>(g, d, s, (const float4 *)(smem + L::oCn), sAz, boot, (int2 *)(smem + L::oReg), pre, t, D, r_in,
+        bk_levels<BK, kBkCapN<NC>, kTreeAzLevel<NC>>(g, d, s, sAz, boot, (int2 *)(smem + L::oReg), pre, t, D, r_in,
                   discount, 0, err, ent_r, ent_w, pmn, pmx, tl);
         if (l == 0) {
             xbo[1].mn = pmn;
@@ -5581,7 +5096,7 @@ __global__ __launch_bounds__(kTreeWavesN<NC> * 64) void k_tree(char *base, const
                 // record {node, visits at selection} for the next back-propagation and the scored
                 // children's count (wave 0's epilogue leaves both to this wave)
                 int cur = uni(xi[58]), Dn = 0, x = 0, xprev = 0, px = 0, nbw = 0;
-                tree_select<NC, true>(smem, d, t, gW1, uni(xi[62]), uni(xi[59]), PS, cur, e, Dn, x, xprev, px, nbw);
+                tree_chase<NC, true>(smem, d, t, gW1, uni(xi[62]), uni(xi[59]), PS, cur, e, Dn, x, xprev, px, nbw);
                 auto write_path = [&]() {
                     int2 *gp = d.path() + (size_t)t * PS;
                     const int2 *sPath1 = (const int2 *)(smem + L::oPath);
@@ -5692,11 +5207,6 @@ __global__ __launch_bounds__(kTreeWavesN<NC> * 64) void k_tree(char *base, const
         glds4a(beta + ib, sW);  // (lanes >= A: zero weights, below)
         glds4a(&d.hdr()[t].nxt[l < kNxt ? l : 0], sNxt);
         glds4a((const int *)st + (l < 2 * MZ_S_COUNT ? l : 0), (int *)sSt);
-        // the value-set scalars of the nodes (the back-propagation waves' path nodes read them)
-        if constexpr (kTreeCStage && !kTreeCW4<NC>)
-        for (int i0 = 0; i0 < ne; i0 += kWave)
-            if (i0 + l < ne)
-                asm volatile("s_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, off" ::"v"(d.C() + nb + i0 + l), "s"(lds_addr(smem) + (unsigned)(L::oCn + 16 * i0)) : "memory", "m0");
     }
     const float t00 = ldsc(d.T());  // pb_c(0, 0): the coefficient of the leaf's new children
     TreeHdr h;
@@ -5795,7 +5305,7 @@ __global__ __launch_bounds__(kTreeWavesN<NC> * 64) void k_tree(char *base, const
     } else {
         double *sp = (double *)(smem + L::oP);
         wait_lds();
-        const double cp = kTreeHelperCdf ? ((const double *)(smem + L::oU))[l] : cdf_staged(A, sW, sp);
+        const double cp = cdf_staged(A, sW, sp);
         if (MZ_STAMPS) {
             asm volatile("" ::"v"(cp));
             stamp(tq, 1);
@@ -5977,7 +5487,6 @@ __global__ __launch_bounds__(kTreeWavesN<NC> * 64) void k_tree(char *base, const
         int par_hsx = xb.w;
         pvv = wl(pvv, xv, 0);
         const int lim8 = PS < kWave ? PS : kWave;  // (walk_step8: path lanes)
-        (void)lim8;
         while (true) {
             MZ_WALK_TOP();
             x = uni(x);
@@ -5986,7 +5495,6 @@ __global__ __launch_bounds__(kTreeWavesN<NC> * 64) void k_tree(char *base, const
             const int nc = uni(nc_of(xb.y));
             if (nc == 0) break;
             const int fc = uni(xb.x);
-#ifndef MZ_NO_WALK2
             if (nc <= 7) {
 #ifdef MZ_STAMPS_SEG
                 asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
@@ -6146,7 +5654,6 @@ __global__ __launch_bounds__(kTreeWavesN<NC> * 64) void k_tree(char *base, const
                 MZ_SEG(sg4);
                 continue;
             }
-#endif
             // the children's records (lane j = child j), the next level's structure record included
             const bool has = l < nc;
             int4 ca = make_int4(0, 0, 0, 0), cb = ca;
@@ -6277,7 +5784,7 @@ __global__ __launch_bounds__(kTreeWavesN<NC> * 64) void k_tree(char *base, const
         stamp(ts, 5);
     if (!err) {
         int xprev = 0;
-        tree_select<NC, true>(smem, d, t, gW, wbase, wsh, PS, cursor, err, Dn, x, xprev, px, nbeyond);
+        tree_chase<NC, true>(smem, d, t, gW, wbase, wsh, PS, cursor, err, Dn, x, xprev, px, nbeyond);
         out_idx = uni(sB[Dn == 0 ? 0 : xprev].w);  // parent->hidden_state_index_x
         out_act = act_of(uni(sB[x].y));            // children_action of the last edge
     }
@@ -7184,11 +6691,9 @@ int launch_step(mz_batch *b, bool eb, bool sel, StepArgs a) {
         ++b->expansions;
         return MZ_OK;
     }
-#ifndef MZ_NO_JOINT
     if (b->N > 1) {
         launch_nc<0, true>(b, eb, sel, a);
     } else
-#endif
     switch (b->nc) {
         case 64: launch_nc<64>(b, eb, sel, a); break;
         case 128: launch_nc<128>(b, eb, sel, a); break;
@@ -7513,9 +7018,6 @@ int mz_create(int B, int N, int A, int K, int S, float delta_lb, uint32_t seed, 
     }
     g.TT = (int)table_entries((unsigned)g.PS);
     g.use_table = (g.PS <= (int)kTableFullPS && 4ll * g.TT <= kTableLdsMax) ? 1 : 0;
-#ifdef MZ_NO_TABLE
-    g.use_table = 0;
-#endif
     auto lay = [&]() {
     int o = 0;
     g.oA = o; o += round16(16 * g.P);
@@ -7567,9 +7069,6 @@ int mz_create(int B, int N, int A, int K, int S, float delta_lb, uint32_t seed, 
             b->nc = nc;
             break;
         }
-#ifdef MZ_DYNAMIC_LAYOUT
-    b->nc = 0;
-#endif
     if (N > 1) b->nc = 0;  // joint-action trees use the general layout (joint regions from Geo)
     if (b->nc) {
         g.use_table = 0;
@@ -7708,10 +7207,8 @@ int mz_create(int B, int N, int A, int K, int S, float delta_lb, uint32_t seed, 
             (void)hipFuncSetAttribute((const void *)k_prepare, hipFuncAttributeMaxDynamicSharedMemorySize, jl);
     }
     if (!b->hbm && g.lds > 64 * 1024) {
-#ifndef MZ_NO_JOINT
         if (N > 1) set_lds_limit<0, true>(g.lds);
         else
-#endif
         switch (b->nc) {
             case 64: set_lds_limit<64>(g.lds); break;
             case 128: set_lds_limit<128>(g.lds); break;

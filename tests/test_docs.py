@@ -48,6 +48,29 @@ def test_named_files_exist(doc):
     assert not missing, f"{doc} names files that do not exist: {missing}"
 
 
+def test_build_switches_are_the_documented_ones():
+    """Every MZ_* name a preprocessor conditional of the kernel sources tests is a row of DESIGN §3's
+    compile-time switch table, and the other way round: a new knob has to be documented."""
+    csrc = os.path.join(ROOT, "mazero_amd", "csrc")
+    used = set()
+    for name in sorted(os.listdir(csrc)):
+        if not name.endswith((".hip", ".inc", ".h")):
+            continue
+        with open(os.path.join(csrc, name)) as f:
+            text = re.sub(r"\\[ \t]*\n", " ", f.read())  # a directive continued with a backslash is one line
+        for line in text.splitlines():
+            m = re.match(r"\s*#\s*(ifdef|ifndef|if|elif)\b(.*)", line)
+            if m:
+                cond = re.sub(r"//.*|/\*.*?\*/", "", m.group(2))
+                used |= set(re.findall(r"\bMZ_[A-Z0-9_]+\b", cond))
+    text = _read("DESIGN.md")
+    sec = text[text.index("### Build switches"):text.index("## 4. Parity and the oracle")]
+    table = sec[sec.index("| Compile-time switch |"):sec.index("| Run-time flag")]
+    listed = set(re.findall(r"^\| `(MZ_[A-Z0-9_]+)` \|", table, flags=re.M))
+    assert listed, "DESIGN §3's compile-time switch table"
+    assert used == listed, (sorted(used - listed), sorted(listed - used))
+
+
 def _bench(config: str) -> dict:
     with open(os.path.join(ROUND, config, "bench.json")) as f:
         return json.loads(f.readline())
