@@ -10,7 +10,8 @@
  * the whole simulation loop runs without a host round trip.  Float results are bit-identical to
  * the numpy expressions on x86-64 numpy 2.x: the exponential restates numpy's float32 SIMD exp
  * (Cody-Waite reduction, rational minimax P5/Q2 with FMAs, 2^k scaling); sums restate numpy's
- * pairwise summation (8 interleaved accumulators below 128 elements); float16 inputs follow
+ * pairwise summation (8 interleaved accumulators up to 128 elements; longer rows split as numpy
+ * splits them, see the _wide entry points); float16 inputs follow
  * numpy's half loops (every operation evaluated in float32 and rounded to half).  With
  * sampled_tau != 1 (the reference always passes 1.0, core/config.py:403-404) the power is the
  * correctly rounded pow of x and 1 / sampled_tau cast to the array's dtype (NEP 50).  That is
@@ -105,6 +106,34 @@ int mz_root_glue(mz_batch *b, const void *logits, int dtype, int64_t row_stride,
  * current_agent); joint_out: int64 [B, num_agents]. */
 int mz_joint_action(mz_batch *b, const void *pred_logits, int dtype, int num_agents, int current_agent,
                     const int32_t *factor, int factor_cols, const int32_t *actions, int64_t *joint_out);
+
+/* Action spaces past 64 (the handle takes up to 255): mz_policy_glue_wide, mz_root_glue_wide and
+ * mz_joint_action_wide have the signatures, argument checks and results of mz_policy_glue,
+ * mz_root_glue and mz_joint_action and accept any action_space_size the handle has (1..255).
+ *   A <= 64: they launch the same kernels as the narrow entry points (one lane per action), so the
+ *     results are identical by construction.
+ *   A  > 64: one wave per root still; lane l holds the actions l + 64 j, j < ceil(A / 64).  The
+ *     elementwise arithmetic is unchanged.  np.sum of a row of n > 128 elements follows numpy's
+ *     pairwise recursion (n2 = n / 2, n2 -= n2 % 8; sum(a, n2) + sum(a + n2, n - n2)): at most three
+ *     base-case blocks for n <= 255, joined as s0 + s1 or s0 + (s1 + s2).  np.max is the row's NaN
+ *     when it holds one (its first in action order), and the softmax of such a row is that NaN in
+ *     every element, sign and payload as numpy on x86-64 leaves them; np.argmax is the smallest
+ *     action holding a NaN, else the smallest action equal to the maximum.
+ * The narrow entry points keep refusing A > 64 (MZ_ERR_UNSUPPORTED, "action_space_size > 64"): two
+ * tests pin that refusal (tests/test_gpu_parity.py, tests/test_driver.py), so the wide path is a
+ * separate set of entry points that a driver opts into (mazero_amd.mcts_sampled, wide_actions). */
+int mz_policy_glue_wide(mz_batch *b, const void *logits, int dtype, int64_t row_stride, int64_t col_offset,
+                        double sampled_tau, float *probs_out, float *beta_out);
+int mz_root_glue_wide(mz_batch *b, const void *logits, int dtype, int64_t row_stride, int64_t col_offset,
+                      const int32_t *legal, int64_t legal_stride, const float *noises, double noise_eps,
+                      double sampled_tau, float *probs_out, float *beta_out, float *noises_out);
+int mz_joint_action_wide(mz_batch *b, const void *pred_logits, int dtype, int num_agents, int current_agent,
+                         const int32_t *factor, int factor_cols, const int32_t *actions, int64_t *joint_out);
+
+/* The base-case blocks the wide kernels sum a row of n elements in (1 <= n <= 255), as the launchers
+ * compute them: starts[3], lens[3] (unused entries 0) and their count.  Host only, no device call;
+ * for the tests that check the plan against np.sum. */
+int mz_wide_sum_plan(int n, int32_t *starts, int32_t *lens, int32_t *num_blocks);
 
 /* Census of a captured, not yet instantiated HIP graph (`graph` is a hipGraph_t): its node count
  * and how many of them are runtime memset nodes, child-graph nodes' graphs counted recursively.

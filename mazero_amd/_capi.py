@@ -114,6 +114,11 @@ DRIVER_SIGNATURES = {
     "mz_policy_glue": (_i, [_p, _p, _i, _i64, _i64, C.c_double, _p, _p]),
     "mz_root_glue": (_i, [_p, _p, _i, _i64, _i64, _p, _i64, _p, C.c_double, C.c_double, _p, _p, _p]),
     "mz_joint_action": (_i, [_p, _p, _i, _i, _i, _p, _i, _p, _p]),
+    # the same three for any action space the handle has (A <= 255; A <= 64 launches the kernels above)
+    "mz_policy_glue_wide": (_i, [_p, _p, _i, _i64, _i64, C.c_double, _p, _p]),
+    "mz_root_glue_wide": (_i, [_p, _p, _i, _i64, _i64, _p, _i64, _p, C.c_double, C.c_double, _p, _p, _p]),
+    "mz_joint_action_wide": (_i, [_p, _p, _i, _i, _i, _p, _i, _p, _p]),
+    "mz_wide_sum_plan": (_i, [_i, C.POINTER(_i), C.POINTER(_i), C.POINTER(_i)]),
     "mz_graph_census": (_i, [_p, C.POINTER(_i), C.POINTER(_i)]),
     "mz_fused_kernel": (_i, [_p, C.c_char_p, _i]),
     "mz_set_half_exp_table": (_i, [_p]),

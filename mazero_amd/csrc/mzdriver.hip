@@ -21,6 +21,7 @@
 #include <cstdint>
 #include <cstdlib>
 #include <mutex>
+#include <string>
 
 #include "../../include/mzdriver.h"
 #include "mz_internal.h"
@@ -296,6 +297,246 @@ __global__ __launch_bounds__(kWave) void k_joint_action(const void *pred, int N,
     }
 }
 
+// ------------------------------------------------------------------------------------------------
+// Action spaces past one wave (64 < A <= 255): still one wave per root; lane l holds the actions
+// l + 64 j, j < T = ceil(A / 64), in registers (T is a template parameter: the tile loops unroll).
+// The elementwise arithmetic is that of the kernels above; only the row reductions differ.
+//
+// np.sum(axis=-1) of a row of n > 128 elements is no longer one base case: numpy's pairwise sum
+// splits at n2 = n / 2, n2 -= n2 % 8 and adds pairwise(a, n2) + pairwise(a + n2, n - n2),
+// recursively.  For n <= 255 the first half (<= 120) is always a base case and the second (<= 135)
+// splits at most once more, so a row is at most three base-case blocks, each starting at a multiple
+// of 8, joined from the right: s0, s0 + s1 or s0 + (s1 + s2).  The launcher walks the recursion
+// once (sum_plan) and hands the kernel the blocks.
+constexpr int kWideMax = 255;       // the handle's own limit (a node packs its action in 8 bits)
+constexpr int kWideRow = 256;       // LDS row: every index below is < A <= 255
+constexpr int kPairwiseBlock = 128; // numpy's PW_BLOCKSIZE
+constexpr int kMaxBlocks = 3;
+
+struct SumPlan {
+    unsigned start;  // byte b: first element of block b
+    unsigned len;    // byte b: its length (1..128), 0: no such block
+};
+
+// the base-case blocks of numpy's pairwise sum over n elements, in row order; returns their count,
+// or -1 when the join is not the right-nested one the kernels apply (never for n <= 255)
+int sum_plan_blocks(int start, int n, int *starts, int *lens, int k, int cap) {
+    if (n <= kPairwiseBlock) {
+        if (k >= cap) return -1;
+        starts[k] = start;
+        lens[k] = n;
+        return k + 1;
+    }
+    int n2 = n / 2;
+    n2 -= n2 % 8;
+    if (n2 > kPairwiseBlock) return -1;  // a left half that splits: (s0 + s1) + ..., not restated
+    k = sum_plan_blocks(start, n2, starts, lens, k, cap);
+    if (k < 0) return k;
+    return sum_plan_blocks(start + n2, n - n2, starts, lens, k, cap);
+}
+
+bool sum_plan(int n, SumPlan *plan) {
+    int starts[kMaxBlocks] = {0, 0, 0}, lens[kMaxBlocks] = {0, 0, 0};
+    if (n < 1 || n > kWideMax || sum_plan_blocks(0, n, starts, lens, 0, kMaxBlocks) < 1) return false;
+    plan->start = (unsigned)starts[0] | (unsigned)starts[1] << 8 | (unsigned)starts[2] << 16;
+    plan->len = (unsigned)lens[0] | (unsigned)lens[1] << 8 | (unsigned)lens[2] << 16;
+    return true;
+}
+
+// np.sum over the row whose element l + 64 j is v[j]; result in every lane.  Lanes 8 b + i run
+// accumulator i of block b; the 8 accumulators combine as a butterfly, which is numpy's
+// ((r0+r1)+(r2+r3))+((r4+r5)+(r6+r7)) in every lane of the group (float addition commutes); lane 8 b
+// adds the block's n % 8 tail; the block sums join from the right.
+template <int T>
+__device__ float np_row_sum_wide(const float (&v)[T], int l, int A, SumPlan plan, float *lds) {
+#pragma unroll
+    for (int j = 0; j < T; ++j)
+        if (l + kWave * j < A) lds[l + kWave * j] = v[j];
+    __syncthreads();
+    const int blk = l >> 3, i = l & 7;
+    const int start = blk < kMaxBlocks ? (int)(plan.start >> (8 * blk) & 0xffu) : 0;
+    const int len = blk < kMaxBlocks ? (int)(plan.len >> (8 * blk) & 0xffu) : 0;
+    // (a block of a row of more than 64 elements holds at least 64: numpy's sequential sum of fewer
+    // than 8 elements never applies here; lanes past the last block idle with len = 0)
+    const int n8 = len - len % 8;
+    float r = 0.f;
+    if (len) {
+        r = lds[start + i];
+        for (int k = 8; k < n8; k += 8) r += lds[start + k + i];
+    }
+    r += __shfl_xor(r, 1, kWave);
+    r += __shfl_xor(r, 2, kWave);
+    r += __shfl_xor(r, 4, kWave);
+    if (i == 0)
+        for (int k = n8; k < len; ++k) r += lds[start + k];
+    const float s0 = __shfl(r, 0, kWave), s1 = __shfl(r, 8, kWave), s2 = __shfl(r, 16, kWave);
+    __syncthreads();  // (the row is read: the next sum may overwrite it)
+    if (plan.len >> 16) return s0 + (s1 + s2);
+    if (plan.len >> 8) return s0 + s1;
+    return s0;
+}
+
+// np.max(axis=-1) of the row: a NaN anywhere makes it that NaN (one ballot per tile; the first in
+// action order where the row holds several)
+template <int T>
+__device__ __forceinline__ float np_row_max_wide(const float (&x)[T], int l, int A) {
+    bool nan_any = false;
+    float m = -INFINITY, nan_v = 0.f;
+#pragma unroll
+    for (int j = 0; j < T; ++j) {
+        const bool on = l + kWave * j < A;
+        const unsigned long long nan_mask = __ballot(on && (x[j] != x[j]));
+        if (!nan_any && nan_mask) {  // (wave-uniform)
+            nan_any = true;
+            nan_v = __shfl(x[j], __ffsll((long long)nan_mask) - 1, kWave);
+        }
+        m = fmaxf(m, on ? x[j] : -INFINITY);
+    }
+    return nan_any ? nan_v : wave_max(m);
+}
+
+// `x - m` of the softmax, m the row's maximum.  When m is a NaN numpy's result is a NaN operand as it
+// stands (x's own where x is one), sign included; the GPU's subtraction negates its second operand
+// first, a NaN's sign with it, so that case is picked by hand.
+__device__ __forceinline__ float np_sub_max(float x, float m) {
+    if (m != m) return (x != x) ? x : m;
+    return x - m;
+}
+
+// k_policy_glue for 64 < A <= 255
+template <bool F16, int T>
+__global__ __launch_bounds__(kWave) void k_policy_glue_wide(const void *logits, long long row_stride,
+                                                            long long col_off, int A, SumPlan plan, int use_pow,
+                                                            float tau_inv, float *probs, float *beta,
+                                                            const unsigned short *hexp) {
+    __shared__ float lds[kWideRow];
+    const int t = blockIdx.x;
+    const int l = threadIdx.x;
+    float x[T], e[T], p[T], q[T];
+#pragma unroll
+    for (int j = 0; j < T; ++j) {
+        const int a = l + kWave * j;
+        x[j] = a < A ? load_elem<F16>(logits, (long long)t * row_stride + col_off + a) : -INFINITY;
+    }
+    const float m = np_row_max_wide<T>(x, l, A);
+#pragma unroll
+    for (int j = 0; j < T; ++j) e[j] = np_exp_as<F16>(round_as<F16>(np_sub_max(x[j], m)), hexp);
+    const float s = round_as<F16>(np_row_sum_wide<T>(e, l, A, plan, lds));
+#pragma unroll
+    for (int j = 0; j < T; ++j) {
+        p[j] = round_as<F16>(e[j] / s);
+        q[j] = use_pow ? np_pow_as<F16>(p[j], tau_inv, use_pow) : p[j];
+    }
+    const float s2 = round_as<F16>(np_row_sum_wide<T>(q, l, A, plan, lds));
+#pragma unroll
+    for (int j = 0; j < T; ++j) {
+        const int a = l + kWave * j;
+        if (a < A) {
+            probs[(long long)t * A + a] = p[j];
+            beta[(long long)t * A + a] = round_as<F16>(q[j] / s2);
+        }
+    }
+}
+
+// k_root_glue for 64 < A <= 255
+template <bool F16, int T>
+__global__ __launch_bounds__(kWave) void k_root_glue_wide(const void *logits, long long row_stride, long long col_off,
+                                                          int A, SumPlan plan, const int *legal,
+                                                          long long legal_stride, const float *noise_in,
+                                                          double one_minus_eps, double eps, int use_pow,
+                                                          float tau_inv, float *probs, float *beta,
+                                                          float *noise_out, const unsigned short *hexp) {
+    __shared__ float lds[kWideRow];
+    const int t = blockIdx.x;
+    const int l = threadIdx.x;
+    float x[T], p[T], n[T], b[T];
+    double lg[T];
+#pragma unroll
+    for (int j = 0; j < T; ++j) {
+        const int a = l + kWave * j;
+        x[j] = a < A ? load_elem<F16>(logits, (long long)t * row_stride + col_off + a) : -INFINITY;
+        n[j] = a < A ? noise_in[(long long)t * A + a] : 0.f;
+        lg[j] = (legal && a < A) ? (double)legal[(long long)t * legal_stride + a] : 0.0;
+    }
+    const float m = np_row_max_wide<T>(x, l, A);
+#pragma unroll
+    for (int j = 0; j < T; ++j) p[j] = np_exp_as<F16>(round_as<F16>(np_sub_max(x[j], m)), hexp);
+    const float s = round_as<F16>(np_row_sum_wide<T>(p, l, A, plan, lds));
+#pragma unroll
+    for (int j = 0; j < T; ++j) p[j] = round_as<F16>(p[j] / s);
+    if (legal) {
+#pragma unroll
+        for (int j = 0; j < T; ++j) {
+            const double tiny = lg[j] * 1e-4;  // `legal * 1e-4`: a float64 array
+            p[j] = store_d<F16>((double)p[j] * lg[j]);
+            p[j] = store_d<F16>((double)p[j] + tiny);
+            n[j] = (float)((double)n[j] * lg[j]);
+            n[j] = (float)((double)n[j] + tiny);
+        }
+        const float sp = round_as<F16>(np_row_sum_wide<T>(p, l, A, plan, lds));
+        const float sn = np_row_sum_wide<T>(n, l, A, plan, lds);
+#pragma unroll
+        for (int j = 0; j < T; ++j) {
+            p[j] = round_as<F16>(p[j] / sp);
+            n[j] = n[j] / sn;
+        }
+    }
+    const float c1 = store_d<F16>(one_minus_eps), c2 = (float)eps;
+#pragma unroll
+    for (int j = 0; j < T; ++j) {
+        const float a1 = round_as<F16>(p[j] * c1);
+        b[j] = a1 + n[j] * c2;
+        if (use_pow) b[j] = np_pow_as<false>(b[j], tau_inv, use_pow);  // a float32 array
+        if (legal) b[j] = (float)((double)b[j] * lg[j]);
+    }
+    const float sb = np_row_sum_wide<T>(b, l, A, plan, lds);
+#pragma unroll
+    for (int j = 0; j < T; ++j) {
+        const int a = l + kWave * j;
+        if (a < A) {
+            probs[(long long)t * A + a] = p[j];
+            beta[(long long)t * A + a] = b[j] / sb;
+            noise_out[(long long)t * A + a] = n[j];
+        }
+    }
+}
+
+// k_joint_action for 64 < A <= 255.  np.argmax: the smallest action holding a NaN if there is one,
+// else the smallest action equal to the maximum.  Action l + 64 j orders by tile first, so the
+// tiles are scanned in order and the first set ballot bit taken inside a tile.
+template <bool F16, int T>
+__global__ __launch_bounds__(kWave) void k_joint_action_wide(const void *pred, int N, int A, int cur,
+                                                             const int *factor, int fcols, const int *actions,
+                                                             long long *joint) {
+    const int t = blockIdx.x;
+    const int l = threadIdx.x;
+    if (l < N && l <= cur) joint[(long long)t * N + l] = (l < cur) ? (long long)factor[(long long)t * fcols + l]
+                                                                    : (long long)actions[t];
+    for (int k = cur + 1; k < N; ++k) {
+        float v[T];
+        float m = -INFINITY;
+        int idx = -1;
+#pragma unroll
+        for (int j = 0; j < T; ++j) {
+            const int a = l + kWave * j;
+            const bool on = a < A;
+            v[j] = on ? load_elem<F16>(pred, ((long long)t * N + k) * A + a) : -INFINITY;
+            m = fmaxf(m, v[j]);
+            const unsigned long long nan_mask = __ballot(on && (v[j] != v[j]));
+            if (idx < 0 && nan_mask) idx = kWave * j + __ffsll((long long)nan_mask) - 1;
+        }
+        if (idx < 0) {  // (wave-uniform)
+            m = wave_max(m);
+#pragma unroll
+            for (int j = 0; j < T; ++j) {
+                const unsigned long long hit = __ballot(l + kWave * j < A && v[j] == m);
+                if (idx < 0 && hit) idx = kWave * j + __ffsll((long long)hit) - 1;
+            }
+        }
+        if (l == 0) joint[(long long)t * N + k] = idx;
+    }
+}
+
 // the table of mz_set_half_exp_table per device (allocated once, never freed: captured graphs keep
 // its address)
 constexpr int kMaxDevices = 64;
@@ -332,85 +573,147 @@ int mz_set_half_exp_table(const uint16_t *table) {
     return MZ_OK;
 }
 
-int mz_policy_glue(mz_batch *b, const void *logits, int dtype, int64_t row_stride, int64_t col_offset,
-                   double sampled_tau, float *probs_out, float *beta_out) {
+// The launchers.  `fn` names the entry point in the messages; `wide` (the _wide entry points) takes
+// any A the handle has and launches the kernels above for A > 64, the one-lane-per-action kernels
+// otherwise, so that A <= 64 computes the same through either entry point.
+static int glue_fail(int code, const char *fn, const char *what) {
+    return mz_internal_fail(code, (std::string(fn) + ": " + what).c_str());
+}
+
+// T = ceil(A / 64) in {2, 3, 4} as a template argument of a wide kernel
+#define MZ_WIDE_TILES(A, LAUNCH)          \
+    do {                                  \
+        switch (((A) + kWave - 1) / kWave) { \
+            case 2: LAUNCH(2); break;     \
+            case 3: LAUNCH(3); break;     \
+            default: LAUNCH(4); break;    \
+        }                                 \
+    } while (0)
+
+static int policy_glue(const char *fn, bool wide, mz_batch *b, const void *logits, int dtype, int64_t row_stride,
+                       int64_t col_offset, double sampled_tau, float *probs_out, float *beta_out) {
     int B = 0, A = 0;
     hipStream_t stream = nullptr;
     int rc = mz_internal_launch_info(b, &B, &A, &stream);
     if (rc) return rc;
-    if (A > kWave)  // (one lane per action; the tree itself takes up to 255 actions)
-        return mz_internal_fail(MZ_ERR_UNSUPPORTED, "mz_policy_glue: action_space_size > 64");
-    if (!logits || !probs_out || !beta_out) return mz_internal_fail(MZ_ERR_ARG, "mz_policy_glue: null buffer");
-    if (dtype != MZ_DT_F32 && dtype != MZ_DT_F16) return mz_internal_fail(MZ_ERR_ARG, "mz_policy_glue: bad dtype");
+    if (!wide && A > kWave)  // (one lane per action; the tree itself takes up to 255 actions)
+        return glue_fail(MZ_ERR_UNSUPPORTED, fn, "action_space_size > 64");
+    SumPlan plan{};
+    if (A > kWave && !sum_plan(A, &plan)) return glue_fail(MZ_ERR_UNSUPPORTED, fn, "action_space_size > 255");
+    if (!logits || !probs_out || !beta_out) return glue_fail(MZ_ERR_ARG, fn, "null buffer");
+    if (dtype != MZ_DT_F32 && dtype != MZ_DT_F16) return glue_fail(MZ_ERR_ARG, fn, "bad dtype");
     if (row_stride < A || col_offset < 0 || col_offset + A > row_stride)
-        return mz_internal_fail(MZ_ERR_ARG, "mz_policy_glue: logits row does not hold the agent's actions");
-    if (!(sampled_tau > 0.0)) return mz_internal_fail(MZ_ERR_ARG, "mz_policy_glue: sampled_tau must be > 0");
+        return glue_fail(MZ_ERR_ARG, fn, "logits row does not hold the agent's actions");
+    if (!(sampled_tau > 0.0)) return glue_fail(MZ_ERR_ARG, fn, "sampled_tau must be > 0");
     const double inv = 1.0 / sampled_tau;  // Python's `1 / sampled_tau`, cast to the array's dtype
     const float tau_inv = (dtype == MZ_DT_F16) ? (float)(_Float16)inv : (float)inv;
     const int use_pow = pow_mode(inv);
-    if (dtype == MZ_DT_F16)
+    const unsigned short *hexp = half_exp_table();
+    if (A > kWave) {
+#define MZ_LAUNCH(T)                                                                                              \
+    if (dtype == MZ_DT_F16)                                                                                       \
+        hipLaunchKernelGGL((k_policy_glue_wide<true, T>), dim3(B), dim3(kWave), 0, stream, logits,                \
+                           (long long)row_stride, (long long)col_offset, A, plan, use_pow, tau_inv, probs_out,    \
+                           beta_out, hexp);                                                                       \
+    else                                                                                                          \
+        hipLaunchKernelGGL((k_policy_glue_wide<false, T>), dim3(B), dim3(kWave), 0, stream, logits,               \
+                           (long long)row_stride, (long long)col_offset, A, plan, use_pow, tau_inv, probs_out,    \
+                           beta_out, hexp)
+        MZ_WIDE_TILES(A, MZ_LAUNCH);
+#undef MZ_LAUNCH
+    } else if (dtype == MZ_DT_F16)
         hipLaunchKernelGGL(k_policy_glue<true>, dim3(B), dim3(kWave), 0, stream, logits, (long long)row_stride,
-                           (long long)col_offset, A, use_pow, tau_inv, probs_out, beta_out, half_exp_table());
+                           (long long)col_offset, A, use_pow, tau_inv, probs_out, beta_out, hexp);
     else
         hipLaunchKernelGGL(k_policy_glue<false>, dim3(B), dim3(kWave), 0, stream, logits, (long long)row_stride,
-                           (long long)col_offset, A, use_pow, tau_inv, probs_out, beta_out, half_exp_table());
+                           (long long)col_offset, A, use_pow, tau_inv, probs_out, beta_out, hexp);
     mz_internal_enqueued(b);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return mz_internal_fail(MZ_ERR_DEVICE, hipGetErrorString(e));
     return MZ_OK;
 }
 
-int mz_root_glue(mz_batch *b, const void *logits, int dtype, int64_t row_stride, int64_t col_offset,
-                 const int32_t *legal, int64_t legal_stride, const float *noises, double noise_eps,
-                 double sampled_tau, float *probs_out, float *beta_out, float *noises_out) {
+static int root_glue(const char *fn, bool wide, mz_batch *b, const void *logits, int dtype, int64_t row_stride,
+                     int64_t col_offset, const int32_t *legal, int64_t legal_stride, const float *noises,
+                     double noise_eps, double sampled_tau, float *probs_out, float *beta_out, float *noises_out) {
     int B = 0, A = 0;
     hipStream_t stream = nullptr;
     int rc = mz_internal_launch_info(b, &B, &A, &stream);
     if (rc) return rc;
-    if (A > kWave)  // (one lane per action; the tree itself takes up to 255 actions)
-        return mz_internal_fail(MZ_ERR_UNSUPPORTED, "mz_root_glue: action_space_size > 64");
-    if (!logits || !noises || !probs_out || !beta_out || !noises_out)
-        return mz_internal_fail(MZ_ERR_ARG, "mz_root_glue: null buffer");
-    if (dtype != MZ_DT_F32 && dtype != MZ_DT_F16) return mz_internal_fail(MZ_ERR_ARG, "mz_root_glue: bad dtype");
+    if (!wide && A > kWave)  // (one lane per action; the tree itself takes up to 255 actions)
+        return glue_fail(MZ_ERR_UNSUPPORTED, fn, "action_space_size > 64");
+    SumPlan plan{};
+    if (A > kWave && !sum_plan(A, &plan)) return glue_fail(MZ_ERR_UNSUPPORTED, fn, "action_space_size > 255");
+    if (!logits || !noises || !probs_out || !beta_out || !noises_out) return glue_fail(MZ_ERR_ARG, fn, "null buffer");
+    if (dtype != MZ_DT_F32 && dtype != MZ_DT_F16) return glue_fail(MZ_ERR_ARG, fn, "bad dtype");
     if (row_stride < A || col_offset < 0 || col_offset + A > row_stride)
-        return mz_internal_fail(MZ_ERR_ARG, "mz_root_glue: logits row does not hold the agent's actions");
-    if (legal && legal_stride < A) return mz_internal_fail(MZ_ERR_ARG, "mz_root_glue: legal rows hold fewer than A");
-    if (!(sampled_tau > 0.0)) return mz_internal_fail(MZ_ERR_ARG, "mz_root_glue: sampled_tau must be > 0");
+        return glue_fail(MZ_ERR_ARG, fn, "logits row does not hold the agent's actions");
+    if (legal && legal_stride < A) return glue_fail(MZ_ERR_ARG, fn, "legal rows hold fewer than A");
+    if (!(sampled_tau > 0.0)) return glue_fail(MZ_ERR_ARG, fn, "sampled_tau must be > 0");
     const double inv = 1.0 / sampled_tau;  // beta is a float32 array here (:93)
     const float tau_inv = (float)inv;
     const int use_pow = pow_mode(inv);
     const double ome = 1.0 - noise_eps;  // (Python float arithmetic)
-    if (dtype == MZ_DT_F16)
+    const unsigned short *hexp = half_exp_table();
+    if (A > kWave) {
+#define MZ_LAUNCH(T)                                                                                              \
+    if (dtype == MZ_DT_F16)                                                                                       \
+        hipLaunchKernelGGL((k_root_glue_wide<true, T>), dim3(B), dim3(kWave), 0, stream, logits,                  \
+                           (long long)row_stride, (long long)col_offset, A, plan, (const int *)legal,             \
+                           (long long)legal_stride, noises, ome, noise_eps, use_pow, tau_inv, probs_out,          \
+                           beta_out, noises_out, hexp);                                                           \
+    else                                                                                                          \
+        hipLaunchKernelGGL((k_root_glue_wide<false, T>), dim3(B), dim3(kWave), 0, stream, logits,                 \
+                           (long long)row_stride, (long long)col_offset, A, plan, (const int *)legal,             \
+                           (long long)legal_stride, noises, ome, noise_eps, use_pow, tau_inv, probs_out,          \
+                           beta_out, noises_out, hexp)
+        MZ_WIDE_TILES(A, MZ_LAUNCH);
+#undef MZ_LAUNCH
+    } else if (dtype == MZ_DT_F16)
         hipLaunchKernelGGL(k_root_glue<true>, dim3(B), dim3(kWave), 0, stream, logits, (long long)row_stride,
                            (long long)col_offset, A, (const int *)legal, (long long)legal_stride, noises, ome,
-                           noise_eps, use_pow, tau_inv, probs_out, beta_out, noises_out, half_exp_table());
+                           noise_eps, use_pow, tau_inv, probs_out, beta_out, noises_out, hexp);
     else
         hipLaunchKernelGGL(k_root_glue<false>, dim3(B), dim3(kWave), 0, stream, logits, (long long)row_stride,
                            (long long)col_offset, A, (const int *)legal, (long long)legal_stride, noises, ome,
-                           noise_eps, use_pow, tau_inv, probs_out, beta_out, noises_out, half_exp_table());
+                           noise_eps, use_pow, tau_inv, probs_out, beta_out, noises_out, hexp);
     mz_internal_enqueued(b);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return mz_internal_fail(MZ_ERR_DEVICE, hipGetErrorString(e));
     return MZ_OK;
 }
 
-int mz_joint_action(mz_batch *b, const void *pred_logits, int dtype, int num_agents, int current_agent,
-                    const int32_t *factor, int factor_cols, const int32_t *actions, int64_t *joint_out) {
+static int joint_action(const char *fn, bool wide, mz_batch *b, const void *pred_logits, int dtype, int num_agents,
+                        int current_agent, const int32_t *factor, int factor_cols, const int32_t *actions,
+                        int64_t *joint_out) {
     int B = 0, A = 0;
     hipStream_t stream = nullptr;
     int rc = mz_internal_launch_info(b, &B, &A, &stream);
     if (rc) return rc;
-    if (A > kWave)  // (one lane per action; the tree itself takes up to 255 actions)
-        return mz_internal_fail(MZ_ERR_UNSUPPORTED, "mz_joint_action: action_space_size > 64");
+    if (!wide && A > kWave)  // (one lane per action; the tree itself takes up to 255 actions)
+        return glue_fail(MZ_ERR_UNSUPPORTED, fn, "action_space_size > 64");
+    if (A > kWideMax) return glue_fail(MZ_ERR_UNSUPPORTED, fn, "action_space_size > 255");
     if (num_agents < 1 || num_agents > kWave || current_agent < 0 || current_agent >= num_agents)
-        return mz_internal_fail(MZ_ERR_ARG, "mz_joint_action: bad agent index / count");
-    if (!actions || !joint_out) return mz_internal_fail(MZ_ERR_ARG, "mz_joint_action: null buffer");
+        return glue_fail(MZ_ERR_ARG, fn, "bad agent index / count");
+    if (!actions || !joint_out) return glue_fail(MZ_ERR_ARG, fn, "null buffer");
     if (current_agent > 0 && (!factor || factor_cols < current_agent))
-        return mz_internal_fail(MZ_ERR_ARG, "mz_joint_action: factor must hold the previous agents' actions");
+        return glue_fail(MZ_ERR_ARG, fn, "factor must hold the previous agents' actions");
     if (current_agent + 1 < num_agents && !pred_logits)
-        return mz_internal_fail(MZ_ERR_ARG, "mz_joint_action: leaf policy logits required for later agents");
-    if (dtype != MZ_DT_F32 && dtype != MZ_DT_F16) return mz_internal_fail(MZ_ERR_ARG, "mz_joint_action: bad dtype");
-    if (dtype == MZ_DT_F16)
+        return glue_fail(MZ_ERR_ARG, fn, "leaf policy logits required for later agents");
+    if (dtype != MZ_DT_F32 && dtype != MZ_DT_F16) return glue_fail(MZ_ERR_ARG, fn, "bad dtype");
+    if (A > kWave) {
+#define MZ_LAUNCH(T)                                                                                              \
+    if (dtype == MZ_DT_F16)                                                                                       \
+        hipLaunchKernelGGL((k_joint_action_wide<true, T>), dim3(B), dim3(kWave), 0, stream, pred_logits,          \
+                           num_agents, A, current_agent, (const int *)factor, factor_cols,                        \
+                           (const int *)actions, (long long *)joint_out);                                         \
+    else                                                                                                          \
+        hipLaunchKernelGGL((k_joint_action_wide<false, T>), dim3(B), dim3(kWave), 0, stream, pred_logits,         \
+                           num_agents, A, current_agent, (const int *)factor, factor_cols,                        \
+                           (const int *)actions, (long long *)joint_out)
+        MZ_WIDE_TILES(A, MZ_LAUNCH);
+#undef MZ_LAUNCH
+    } else if (dtype == MZ_DT_F16)
         hipLaunchKernelGGL(k_joint_action<true>, dim3(B), dim3(kWave), 0, stream, pred_logits, num_agents, A,
                            current_agent, (const int *)factor, factor_cols, (const int *)actions,
                            (long long *)joint_out);
@@ -421,6 +724,58 @@ int mz_joint_action(mz_batch *b, const void *pred_logits, int dtype, int num_age
     mz_internal_enqueued(b);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return mz_internal_fail(MZ_ERR_DEVICE, hipGetErrorString(e));
+    return MZ_OK;
+}
+
+int mz_policy_glue(mz_batch *b, const void *logits, int dtype, int64_t row_stride, int64_t col_offset,
+                   double sampled_tau, float *probs_out, float *beta_out) {
+    return policy_glue("mz_policy_glue", false, b, logits, dtype, row_stride, col_offset, sampled_tau, probs_out,
+                       beta_out);
+}
+
+int mz_policy_glue_wide(mz_batch *b, const void *logits, int dtype, int64_t row_stride, int64_t col_offset,
+                        double sampled_tau, float *probs_out, float *beta_out) {
+    return policy_glue("mz_policy_glue_wide", true, b, logits, dtype, row_stride, col_offset, sampled_tau,
+                       probs_out, beta_out);
+}
+
+int mz_root_glue(mz_batch *b, const void *logits, int dtype, int64_t row_stride, int64_t col_offset,
+                 const int32_t *legal, int64_t legal_stride, const float *noises, double noise_eps,
+                 double sampled_tau, float *probs_out, float *beta_out, float *noises_out) {
+    return root_glue("mz_root_glue", false, b, logits, dtype, row_stride, col_offset, legal, legal_stride, noises,
+                     noise_eps, sampled_tau, probs_out, beta_out, noises_out);
+}
+
+int mz_root_glue_wide(mz_batch *b, const void *logits, int dtype, int64_t row_stride, int64_t col_offset,
+                      const int32_t *legal, int64_t legal_stride, const float *noises, double noise_eps,
+                      double sampled_tau, float *probs_out, float *beta_out, float *noises_out) {
+    return root_glue("mz_root_glue_wide", true, b, logits, dtype, row_stride, col_offset, legal, legal_stride,
+                     noises, noise_eps, sampled_tau, probs_out, beta_out, noises_out);
+}
+
+int mz_joint_action(mz_batch *b, const void *pred_logits, int dtype, int num_agents, int current_agent,
+                    const int32_t *factor, int factor_cols, const int32_t *actions, int64_t *joint_out) {
+    return joint_action("mz_joint_action", false, b, pred_logits, dtype, num_agents, current_agent, factor,
+                        factor_cols, actions, joint_out);
+}
+
+int mz_joint_action_wide(mz_batch *b, const void *pred_logits, int dtype, int num_agents, int current_agent,
+                         const int32_t *factor, int factor_cols, const int32_t *actions, int64_t *joint_out) {
+    return joint_action("mz_joint_action_wide", true, b, pred_logits, dtype, num_agents, current_agent, factor,
+                        factor_cols, actions, joint_out);
+}
+
+int mz_wide_sum_plan(int n, int32_t *starts, int32_t *lens, int32_t *num_blocks) {
+    if (!starts || !lens || !num_blocks) return mz_internal_fail(MZ_ERR_ARG, "mz_wide_sum_plan: null argument");
+    SumPlan plan{};
+    if (!sum_plan(n, &plan)) return mz_internal_fail(MZ_ERR_UNSUPPORTED, "mz_wide_sum_plan: n outside 1..255");
+    int k = 0;
+    for (int i = 0; i < kMaxBlocks; ++i) {
+        starts[i] = (int32_t)(plan.start >> (8 * i) & 0xffu);
+        lens[i] = (int32_t)(plan.len >> (8 * i) & 0xffu);
+        if (lens[i]) ++k;
+    }
+    *num_blocks = k;
     return MZ_OK;
 }
 

@@ -13,6 +13,9 @@ and the per-simulation glue stay on the device:
     model.dynamics + model.prediction       the model's own kernels, inverse transforms included
     policy softmax + beta                   mz_policy_glue (numpy float32/float16 arithmetic)
 
+(with `wide_actions`: mz_root_glue_wide, mz_joint_action_wide, mz_policy_glue_wide, for action spaces
+of 65..255)
+
 so a search has no host synchronisation between `prepare` and the final readback.  The root
 preprocessing (mcts_sampled.py:51-106) is split: the host draws from `np_random` (the Dirichlet
 noise, then the tree seed, in the reference's order) and packs the raw root inputs into one pinned
@@ -112,8 +115,15 @@ class _SearchLoop:
     Every input is copied into the static buffers before a run, and the tree seed lives in device
     memory (mz_reseed), so replaying the graph is a new search."""
 
-    def __init__(self, tb, B, A, N, cur, hidden, dev, model, root_mode=None):
+    def __init__(self, tb, B, A, N, cur, hidden, dev, model, root_mode=None, wide=False):
         self.tb, self.B, self.A, self.N, self.cur, self.dev = tb, B, A, N, cur, dev
+        # the glue entry points this loop records: the _wide ones take A <= 255 (SampledMCTS's
+        # wide_actions), the narrow ones refuse A > 64
+        sfx = "_wide" if wide else ""
+        lib = tb._lib
+        self.root_glue, self.joint_action, self.policy_glue = (
+            getattr(lib, "mz_root_glue" + sfx), getattr(lib, "mz_joint_action" + sfx),
+            getattr(lib, "mz_policy_glue" + sfx))
         ensure_half_exp(tb._lib, dev.index if dev.index is not None else torch.cuda.current_device())
         self.model_ref = weakref.ref(model)  # the captured graph reads this model's parameters
         self.root = torch.empty_like(hidden.reshape(B, -1))
@@ -195,11 +205,11 @@ class _SearchLoop:
         if self.root_mode is not None:  # root preprocessing on the device, mcts_sampled.py:64-100
             dv = self.dev_view
             lg = dv.get("legal")
-            check(lib, lib.mz_root_glue(h, C.c_void_p(dv["logits"].data_ptr()), self.root_mode[0], A, 0,
-                                        None if lg is None else C.c_void_p(lg.data_ptr()), A,
-                                        C.c_void_p(dv["noise"].data_ptr()), float(eps), float(tau),
-                                        C.c_void_p(r[2].data_ptr()), C.c_void_p(r[3].data_ptr()),
-                                        C.c_void_p(r[4].data_ptr())), "root_glue")
+            check(lib, self.root_glue(h, C.c_void_p(dv["logits"].data_ptr()), self.root_mode[0], A, 0,
+                                      None if lg is None else C.c_void_p(lg.data_ptr()), A,
+                                      C.c_void_p(dv["noise"].data_ptr()), float(eps), float(tau),
+                                      C.c_void_p(r[2].data_ptr()), C.c_void_p(r[3].data_ptr()),
+                                      C.c_void_p(r[4].data_ptr())), "root_glue")
             r = [dv["rewards"], dv["values"], r[2], r[3], r[4]]
         # prepare + the first selection (the root's forced first child) in one launch
         tb.prepare_selection_device(r[0], r[1], r[2], r[3], K, eps, r[4], c2, c1, disc, out=self.sel)
@@ -223,9 +233,9 @@ class _SearchLoop:
                 ptr, dt = C.c_void_p(pred_logits.data_ptr()), _dtype_code(pred_logits)
             else:
                 ptr, dt = None, MZ_DT_F32
-            check(lib, lib.mz_joint_action(h, ptr, dt, N, cur, C.c_void_p(self.fac.data_ptr()),
-                                           self.fac.shape[1], C.c_void_p(act.data_ptr()),
-                                           C.c_void_p(self.joint.data_ptr())), "joint_action")
+            check(lib, self.joint_action(h, ptr, dt, N, cur, C.c_void_p(self.fac.data_ptr()),
+                                         self.fac.shape[1], C.c_void_p(act.data_ptr()),
+                                         C.c_void_p(self.joint.data_ptr())), "joint_action")
             next_h, reward, value, logits = SampledMCTS._recurrent(model, leaf, self.joint)  # :150-156
             nh = next_h.reshape(B, -1)
             chain = K == 1
@@ -247,9 +257,9 @@ class _SearchLoop:
                     self.pool[0].copy_(self.root)
                 self.pool[s + 1].copy_(nh)  # :164
             logits = logits.contiguous()
-            check(lib, lib.mz_policy_glue(h, C.c_void_p(logits.data_ptr()), _dtype_code(logits),
-                                          logits.shape[1] * logits.shape[2], cur * A, float(tau),
-                                          C.c_void_p(self.probs.data_ptr()), C.c_void_p(self.beta.data_ptr())),
+            check(lib, self.policy_glue(h, C.c_void_p(logits.data_ptr()), _dtype_code(logits),
+                                        logits.shape[1] * logits.shape[2], cur * A, float(tau),
+                                        C.c_void_p(self.probs.data_ptr()), C.c_void_p(self.beta.data_ptr())),
                   "policy_glue")
             r32 = reward.reshape(B).float()
             v32 = value.reshape(B).float()
@@ -381,20 +391,34 @@ def _storage_signature(model) -> tuple:
 
 
 MAX_GLUE_ACTIONS = 64  # include/mzdriver.h: the glue kernels hold one action per lane
+MAX_WIDE_ACTIONS = 255  # the _wide glue entry points: every action space the tree itself takes
 
 
 class SampledMCTS:
     """mcts_sampled.py:29-32.  `lib` selects the tree library (default: the MI355X product)."""
 
     def __init__(self, config, np_random: np.random.RandomState = None, *, lib=None, use_graph: bool = True,
-                 root_shard: Tuple[int, int, int] = None, device_root: bool = True):
-        """`root_shard` = (lo, hi, total): this instance searches roots [lo, hi) of a batch of `total`
+                 root_shard: Tuple[int, int, int] = None, device_root: bool = True, wide_actions: bool = None):
+        """`wide_actions`: run the driver glue through the _wide entry points (include/mzdriver.h), which
+        take action spaces up to 255 instead of 64.  None reads `config.wide_actions` (False when the
+        config has none), so a reference-style `SampledMCTS(config, np_random)` opts in through its
+        config object.  Off by default: the refusal of A > 64 below is pinned by the test suite.
+
+        `root_shard` = (lo, hi, total): this instance searches roots [lo, hi) of a batch of `total`
         roots sharded over ranks (mazero_amd.workers).  Every rank holds the same `np_random` state;
         the per-root draws (Dirichlet noise here, select_action's uniforms in consume) are drawn for
         the whole batch and sliced, and tree i is seeded with its global index, so a rank's results
         equal rows [lo, hi) of the unsharded search."""
         self.config = config
-        if int(config.action_space_size) > MAX_GLUE_ACTIONS:
+        if wide_actions is None:
+            wide_actions = getattr(config, "wide_actions", False)
+        self.wide_actions = bool(wide_actions)
+        if self.wide_actions:
+            if int(config.action_space_size) > MAX_WIDE_ACTIONS:
+                raise RuntimeError(f"SampledMCTS: action_space_size {config.action_space_size} > {MAX_WIDE_ACTIONS} "
+                                   "(a tree node packs its action in 8 bits; the wide driver glue and "
+                                   "mazero_amd.cytree.Tree_batch take up to 255)")
+        elif int(config.action_space_size) > MAX_GLUE_ACTIONS:
             # the device driver glue (mz_policy_glue, mz_root_glue, mz_joint_action: one lane per
             # action) refuses wider action spaces; refused here, before any search launches (the
             # drop-in Tree_batch surface itself takes A <= 255)
@@ -568,7 +592,7 @@ class SampledMCTS:
             tb = self._tree(B, seed, dev)
             # the discount is a kernel argument of the recorded launches
             key = (threading.get_ident(), id(tb), id(model), N, cur, float(eps), float(sampled_tau), float(disc),
-                   tuple(hidden.shape), hidden.dtype, root_mode)
+                   tuple(hidden.shape), hidden.dtype, root_mode, self.wide_actions)
             with _LOCK:
                 for k in [k for k, v in _LOOPS.items() if v.model_ref() is None]:
                     del _LOOPS[k]  # loops (graph, pool) of models that no longer exist
@@ -577,7 +601,8 @@ class SampledMCTS:
                 # ids are reused once an object is freed; a recorded graph reads the parameters at the
                 # addresses it was recorded with (re-homed weights, weights.FlatWeights, need a new one)
                 if st is None or st.model_ref() is not model or st.storage != sig or st.tb is not tb:
-                    st = _LOOPS[key] = _SearchLoop(tb, B, A, N, cur, hidden, dev, model, root_mode)
+                    st = _LOOPS[key] = _SearchLoop(tb, B, A, N, cur, hidden, dev, model, root_mode,
+                                                   wide=self.wide_actions)
                     st.storage = sig
                 _LOOPS.move_to_end(key)
                 while len(_LOOPS) > max(_MAX_LOOPS, 1):  # least recently used first

@@ -63,10 +63,10 @@ def _device_reanalyze_decide(mcts, model, network_output, legal, policy_mask, de
     return reanalyze_policy_targets(mcts, model, network_output, legal, policy_mask, device)._asdict()
 
 
-def _default_mcts(config, np_random, root_shard):
+def _default_mcts(config, np_random, root_shard, wide_actions=None):
     from .mcts_sampled import SampledMCTS
 
-    return SampledMCTS(config, np_random, root_shard=root_shard)
+    return SampledMCTS(config, np_random, root_shard=root_shard, wide_actions=wide_actions)
 
 
 @dataclass
@@ -86,7 +86,9 @@ class StepRecord:
 class _Shard:
     def __init__(self, model, config, total: int, *, seed: int, broadcaster=None, group=None, src: int = 0,
                  make_mcts: Optional[Callable] = None, device=None, rank: Optional[int] = None,
-                 world: Optional[int] = None):
+                 world: Optional[int] = None, wide_actions: Optional[bool] = None):
+        """`wide_actions` goes to the default search (SampledMCTS: action spaces up to 255 instead of
+        64; None reads `config.wide_actions`); a `make_mcts` of the caller's decides for itself."""
         self.model, self.config, self.total = model, config, int(total)
         self.rank, self.world = _rank_world(group)
         if rank is not None or world is not None:  # a shard without a process group (single-GPU tests)
@@ -99,7 +101,7 @@ class _Shard:
         # the same generator state on every rank: sharded draws are sliced from whole-batch draws
         self.np_random = np.random.RandomState(seed)
         self.broadcaster, self.src, self.group = broadcaster, src, group
-        self.make_mcts = make_mcts or _default_mcts
+        self.make_mcts = make_mcts or (lambda c, r, s: _default_mcts(c, r, s, wide_actions))
         self.device = device
         self.model_index = -1
         if broadcaster is not None and self.rank == src and broadcaster.model_index < 0:
