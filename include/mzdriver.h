@@ -153,6 +153,12 @@ int mz_graph_census(void *graph, int *total_nodes, int *memset_nodes);
  * MZ_HBM); for the bench's roofline label and the tests that pin which path ran. */
 int mz_fused_kernel(mz_batch *b, char *out, int len);
 
+/* The wavefronts per workgroup of this handle's k_chain3 launches: 4 with the draw wave (the
+ * 64-node class at one workgroup per CU at most, unless MZ_CHAIN3_W3 is set; any k_chain3 handle
+ * under MZ_CHAIN3_W4), else 3; 0 when the handle does not launch
+ * k_chain3.  The name above is the same for both. */
+int mz_fused_waves(mz_batch *b, int *waves);
+
 /* Release what the library keeps for reuse across handles: device arenas of destroyed handles
  * (at most 2 GiB / 16 blocks per process, reused by a handle of the same size, as the reference's
  * per-search Tree_batch re-creates them, mcts_sampled.py:89), pinned host stages (at most

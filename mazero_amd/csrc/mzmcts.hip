@@ -3417,8 +3417,40 @@ int chain3_lds_bytes(int nc) { return Chain3Layout<0>(nc).total; }
 // host passes the leaf's slot (pool + hsx * pool_stride) in the argument src_slot (the first one past
 // the preloaded 14 dwords: one scalar load) and the row size in 16-byte units in the preloaded ppk's
 // top bits: wave 2 issues the row's loads as soon as src_slot has landed, ahead of its scalar round.
-template <int NC, bool SEL, int ROW>
-__global__ __launch_bounds__(192) void k_chain3(char *base, const float *policy, const float *beta, const float *reward,
+//
+// W4: a fourth wave (the draw wave) builds the expansion's distribution and draws the action from
+// launch start, beside wave 0's round 1 -- it needs only this launch's beta row and the header's two
+// engine words, both addressed from the preloaded arguments.  It hands the action to wave 0 through
+// one LDS dword (kDrawSlot of the oX region: bit 31 set, the action below it, one store).  LDS is not
+// cleared between workgroups, so wave 0 clears the slot and one s_barrier, taken by all four waves
+// behind their round-1 load issue and before any early return, separates the clear from the publish.
+// Wave 0 polls the slot a bounded number of times (kDrawPolls); if the bound runs out it draws itself
+// with cdf_lane (no LDS: the draw wave may still be using sW / sP), bit-identical, so a launch can
+// never hang on the hand-over.
+constexpr int kDrawSlot = 4;  // dword of the oX region (0, 1: min / max; stamps from dword 16)
+#ifndef MZ_CHAIN3_POLLS
+#define MZ_CHAIN3_POLLS 128  // ~100 cycles each: several times the draw wave's ~2,000 cycles
+#endif
+constexpr int kDrawPolls = MZ_CHAIN3_POLLS;
+__device__ __forceinline__ void start_barrier() { asm volatile("s_barrier" ::: "memory"); }
+// the slot's accesses: volatile (every poll reads LDS again) and typed as LDS (a volatile access
+// through a generic pointer is a flat one, which also waits for the wave's global stores)
+#ifdef __HIP_DEVICE_COMPILE__
+typedef volatile __attribute__((address_space(3))) int lds_vint;
+#else
+typedef volatile int lds_vint;
+#endif
+__device__ __forceinline__ void draw_slot_set(int *sxi, int v) { *(lds_vint *)(lds_void *)&sxi[kDrawSlot] = v; }
+__device__ __forceinline__ int draw_slot_get(int *sxi) { return *(lds_vint *)(lds_void *)&sxi[kDrawSlot]; }
+// the draw's u from two engine words (generate_canonical<double, 53>, libstdc++ random.tcc:3348-3378)
+__device__ __forceinline__ double draw_u(unsigned n0, unsigned n1) {
+    const double w1 = (double)n0, w2 = (double)n1;
+    double u = (w1 + w2 * 4294967296.0) / 18446744073709551616.0;
+    if (u >= 1.0) u = 0x1.fffffffffffffp-1;  // nextafter(1, 0)
+    return u;
+}
+template <int NC, bool SEL, int ROW, bool W4>
+__global__ __launch_bounds__(W4 ? 256 : 192) void k_chain3(char *base, const float *policy, const float *beta, const float *reward,
                                                 const float *value, int ppk, int bak, int hsx, float discount,
                                                 const char *src_slot, ChainIO io) {
     static_assert(NC >= kWave && NC % kWave == 0 && NC < 1024, "k_chain3 node classes are whole waves, < 1024");
@@ -3456,6 +3488,32 @@ __global__ __launch_bounds__(192) void k_chain3(char *base, const float *policy,
     TreeHdr *hp = d.hdr() + t;
     const int Dp = (hsx >= 0 && hsx + 1 <= P) ? hsx : 0;  // the chain's leaf, if the header agrees
 
+    if constexpr (W4) {
+        if (wv == 3) {
+            // ======== wave 3: the expansion's distribution and draw (cnode.cpp:224-295) ========
+            // Straight-line code: this launch's beta row and the header's two engine words, the
+            // start barrier while they are in flight, the distribution, one LDS store.  No header
+            // check (on a dead or out-of-chain tree wave 0 returns before it reads the slot; the
+            // loads are in bounds for every t), no global store.
+            const float bet = beta[(size_t)t * A + (l < A ? l : 0)];
+            int2v nx = sload2(&hp->nxt[0]);
+            start_barrier();
+            asm volatile("s_waitcnt lgkmcnt(0)" : "+s"(nx) : : "memory");
+            int a = 0;
+            if (A >= 2) {
+                const double cp = cdf_bcast(bet, A, (float *)(smem + L.oW), (double *)(smem + L.oP));
+                const double u = draw_u((unsigned)nx[0], (unsigned)nx[1]);
+                a = __popcll(ballot(l < A && cp < u));  // lower_bound
+            }
+            if (l == 0) {
+                if (MZ_STAMPS) sXl[3] = (long long)(__builtin_amdgcn_s_memtime() - ts[0]);  // this wave's end
+                draw_slot_set(sXi, (int)(0x80000000u | (unsigned)a));
+            }
+            wait_lds();
+            return;
+        }
+    }
+
     if (wv == 1) {
         // ======== wave 1: CTree::back_propagate (cnode.cpp:415-450) over the chain ========
         int8v hv = sload8(hp);  // cursor, tot, D, err, mm_min, mm_max, mm_cnt, leaf
@@ -3483,6 +3541,7 @@ __global__ __launch_bounds__(192) void k_chain3(char *base, const float *policy,
         };
         load(Dp, lpt);  // (one round: every address follows from the preloaded arguments)
         asm volatile("s_waitcnt lgkmcnt(0)" : "+s"(hv), "+s"(r_i), "+s"(v_i)::"memory");
+        if constexpr (W4) start_barrier();  // (every wave, before any return: wave 0's slot clear)
         const float r_in = i2f(r_i), v_in = i2f(v_i);
         const int herr = hv[3], D = hv[2], toth = hv[1], leafh = hv[7];
         if (herr) return;  // (wave 0 reports; no wave takes the barrier on the error paths)
@@ -3614,6 +3673,10 @@ __global__ __launch_bounds__(192) void k_chain3(char *base, const float *policy,
         int16v hv = sload16(hp);  // cursor, tot, D, err, mm_min, mm_max, mm_cnt, leaf, tame, root_vis, leaf_y, hot_tag
         // pool, pool_stride, row_bytes, gather_out, one_minus_rho, o_stats (wave 2's argument line)
         int16v io8 = sload16((const void *)iop);
+        // (every wave takes the start barrier before any return: wave 0's slot clear.  Here ahead of
+        // the wait: this wave's round 1 is two dependent scalar round trips with ROW 1, 2, and the
+        // other waves would wait at the barrier for the second)
+        if constexpr (W4) start_barrier();
         asm volatile("s_waitcnt lgkmcnt(0)" : "+s"(io8), "+s"(hv) : : "memory");
         const int omri = io8[8], osti = io8[9];
         int rv0 = hv[9];
@@ -3706,6 +3769,9 @@ __global__ __launch_bounds__(192) void k_chain3(char *base, const float *policy,
     int r_i = sload1(reward + t), v_i = sload1(value + t);
     const float pol = policy[(size_t)t * A + (l < A ? l : 0)];
     const float bet = beta[(size_t)t * A + (l < A ? l : 0)];
+    if constexpr (W4) {  // the hand-over slot, cleared ahead of the start barrier (round 1's wait covers the store)
+        if (l == 0) draw_slot_set(sXi, 0);
+    }
     arena();
     // This launch's record stores, one per lane, from addresses held in registers: lane 0 the child's
     // C, lane 1 the leaf's Bn, lane 2 the child's A, lane 3 the child's Bn (16 bytes each), and the
@@ -3723,6 +3789,7 @@ __global__ __launch_bounds__(192) void k_chain3(char *base, const float *policy,
                  : "+s"(hv), "+s"(kv), "+s"(r_i), "+s"(v_i)
                  :
                  : "memory");
+    if constexpr (W4) start_barrier();  // (every wave, before any return: the slot is clear from here)
     // The root's visit count and the leaf's Bn.y: the header's copy when the previous launch left a
     // valid one (k_prepare, k_chain3), else the records (one more round trip: the first fused launch
     // after a host-path step, or after any other kernel wrote the header)
@@ -3837,7 +3904,32 @@ __global__ __launch_bounds__(192) void k_chain3(char *base, const float *policy,
         wild_l = tame_prior(prior_l) ? 0 : 1;
         asm volatile("" : "+v"(prior_l), "+v"(wild_l));
     };
-    if (A >= 2) {
+    int fell = 0;  // (stamped builds: hand-overs that ran out of polls)
+    if constexpr (W4) {
+        // the draw wave's action: a bounded poll of the hand-over slot (an LDS read, a readfirstlane
+        // and a scalar test each)
+        priors();
+        early();
+        stamp(ts, 7);
+        int v = 0;
+        for (int i = 0; i < kDrawPolls; ++i) {
+            v = uni(draw_slot_get(sXi));
+            if (v < 0) break;
+        }
+        if (v < 0) {
+            a = v & 0x7fffffff;
+        } else {
+            // the bound ran out: this wave draws itself, in registers (sW / sP may still be the draw
+            // wave's), from the same words in the same order
+            fell = 1;
+            if (A >= 2) {
+                const double cp = cdf_lane((l < A) ? (double)bet : 0.0, A);
+                const double u = draw_u(h.nxt[0], h.nxt[1]);
+                a = __popcll(ballot(l < A && cp < u));  // lower_bound
+            }
+        }
+        if (A >= 2) cursor += 2;
+    } else if (A >= 2) {
         // the draw's u, from the header's two engine words
         double u = 0.0;
         const double cp = cdf_bcast(
@@ -3847,9 +3939,7 @@ __global__ __launch_bounds__(192) void k_chain3(char *base, const float *policy,
                 early();
             },
             [&]() {  // (while its second is)
-                const double w1 = (double)h.nxt[0], w2 = (double)h.nxt[1];
-                u = (w1 + w2 * 4294967296.0) / 18446744073709551616.0;
-                if (u >= 1.0) u = 0x1.fffffffffffffp-1;  // nextafter(1, 0)
+                u = draw_u(h.nxt[0], h.nxt[1]);
                 asm volatile("" : "+v"(u));
             });
         a = __popcll(ballot(l < A && cp < u));  // lower_bound
@@ -3983,6 +4073,11 @@ __global__ __launch_bounds__(192) void k_chain3(char *base, const float *policy,
             case MZ_S_CYC_BAK_BOOT: add = sXl[0]; break;                     // wave 1: recurrence
             case MZ_S_CYC_BAK_NODES: add = sXl[1]; break;                    // wave 1: node updates
             case MZ_S_CYC_W1_ROUND1: add = sXl[2]; break;                    // wave 1: round 1
+            // the draw wave (W4): its end after launch start, wave 0's wait at the hand-over slot
+            // (part of the distribution + draw span above), hand-overs that ran out of polls (a count)
+            case MZ_S_CYC_EXP_DRAW: add = W4 ? sXl[3] : 0; break;
+            case MZ_S_CYC_BAK_WAIT: add = W4 ? (long long)(ts[2] - ts[7]) : 0; break;
+            case MZ_S_CYC_EXP_NODES: add = fell; break;
             case MZ_S_STAMPED: add = 1; break;
             default: break;
         }
@@ -6168,6 +6263,7 @@ struct mz_batch {
     int nc = 0;                // k_step layout class (0 = layout from Geo)
     int chain_nc = -1;         // k_chain node class for K = 1 trees (-1: k_step for every launch)
     int chain3_nc = 0;         // k_chain3 node class (64 .. 1024) for K = 1 trees, 0: k_chain / k_step
+    bool chain3_w4 = false;    // k_chain3 with the draw wave (four waves; mz_create)
     ChainK chain_k{};          // k_chain3's copy of the Params fields its waves read (mz_create)
     int tree_nc = -1;          // k_tree node class for 2 <= K <= 64 trees (-1: k_step)
     bool hbm = false;          // the pool's LDS image exceeds a CU's LDS: every step launch is k_hbm
@@ -6528,7 +6624,7 @@ void launch_chain(mz_batch *b, const StepArgs &a, int lds) {
                        a.reward, a.value, a.pool, a.pool_stride, a.row_bytes, a.gather_out, a.idx_x, a.idy, a.act);
 }
 
-template <int NC, bool SEL, int ROW>
+template <int NC, bool SEL, int ROW, bool W4>
 void launch_chain3_row(mz_batch *b, const StepArgs &a) {
     const Geo &g = b->geo;
     const Dev &dv = b->dev;
@@ -6540,7 +6636,7 @@ void launch_chain3_row(mz_batch *b, const StepArgs &a) {
     const bool pre = ROW == 1 || ROW == 2;
     const char *src_slot = pre ? a.pool + (long long)a.hsx * a.pool_stride : nullptr;
     const int rb16 = pre ? (int)(a.row_bytes / 16) : 0;
-    hipLaunchKernelGGL((k_chain3<NC, SEL, ROW>), dim3(g.B), dim3(3 * kWave),
+    hipLaunchKernelGGL((k_chain3<NC, SEL, ROW, W4>), dim3(g.B), dim3((W4 ? 4 : 3) * kWave),
                        chain3_lds_bytes(NC) + (ROW == 2 ? 16 * 16 * kWave : 0), b->stream, (char *)dv.base, a.policy,
                        a.beta, a.reward, a.value, g.P | (g.PS << 10) | (rb16 << 20),
                        (int)((unsigned)g.B | ((unsigned)g.A << 24) | ((unsigned)b->fast_ok << 31)), a.hsx, a.discount,
@@ -6555,14 +6651,19 @@ int chain3_row(const StepArgs &a, bool sel) {
     if (al && a.row_bytes > 0 && a.row_bytes <= 16 * 16 * kWave) return 2;
     return 0;
 }
+template <int NC, bool SEL, bool W4>
+void launch_chain3_w(mz_batch *b, const StepArgs &a) {
+    switch (chain3_row(a, SEL)) {
+        case 1: launch_chain3_row<NC, SEL, 1, W4>(b, a); break;
+        case 2: launch_chain3_row<NC, SEL, 2, W4>(b, a); break;
+        case 3: launch_chain3_row<NC, SEL, 3, W4>(b, a); break;
+        default: launch_chain3_row<NC, SEL, 0, W4>(b, a); break;
+    }
+}
 template <int NC, bool SEL = true>
 void launch_chain3(mz_batch *b, const StepArgs &a) {
-    switch (chain3_row(a, SEL)) {
-        case 1: launch_chain3_row<NC, SEL, 1>(b, a); break;
-        case 2: launch_chain3_row<NC, SEL, 2>(b, a); break;
-        case 3: launch_chain3_row<NC, SEL, 3>(b, a); break;
-        default: launch_chain3_row<NC, SEL, 0>(b, a); break;
-    }
+    if (b->chain3_w4) launch_chain3_w<NC, SEL, true>(b, a);  // with the draw wave (mz_create)
+    else launch_chain3_w<NC, SEL, false>(b, a);
 }
 
 static int device_cus() {  // compute units of the current device (one MI355X: 256)
@@ -7165,6 +7266,14 @@ int mz_create(int B, int N, int A, int K, int S, float delta_lb, uint32_t seed, 
     // (pools above 256 nodes keep k_chain: wave 1 holds the chain's records in registers, 8 per 64 nodes)
     if (b->chain_nc > 0 && b->chain_nc <= 256 && b->P < 1024 && b->PS < 1024 && !getenv_flag("MZ_CHAIN_V2"))
         b->chain3_nc = b->chain_nc;
+    // the draw wave: in the 64-node class (in the longer chains of the larger classes wave 1 ends
+    // last, and the start barrier holds it until wave 0 arrives: 27m K = 1 measured 2.6 % slower
+    // with it) and while the workgroups fit one per CU (every wave of a workgroup on a SIMD of its
+    // own, as k_tree's wave-1 gather decides: 2s3z's 1,024 roots measured 1.9 % slower with it).
+    // MZ_CHAIN3_W3 keeps the three-wave kernel, MZ_CHAIN3_W4 takes the four-wave one wherever
+    // k_chain3 serves (A/B runs, the tests of the larger classes)
+    b->chain3_w4 = b->chain3_nc > 0 && !getenv_flag("MZ_CHAIN3_W3") &&
+                   ((b->chain3_nc == 64 && B <= device_cus()) || getenv_flag("MZ_CHAIN3_W4"));
     const unsigned *seed_cp = nullptr;
     unsigned seed_cp_n = 0;
     if (!getenv_flag("MZ_NO_SEED_TABLE"))
@@ -7550,6 +7659,12 @@ int mz_fused_kernel(mz_batch *b, char *out, int len) {
     else if (b->N > 1) std::snprintf(name, sizeof name, "k_step<0,joint>");
     else std::snprintf(name, sizeof name, "k_step<%d>", b->nc);
     std::snprintf(out, (size_t)len, "%s", name);
+    return MZ_OK;
+}
+
+int mz_fused_waves(mz_batch *b, int *waves) {
+    if (!b || !waves) return fail(MZ_ERR_ARG, "mz_fused_waves: null argument");
+    *waves = b->chain3_nc > 0 ? (b->chain3_w4 ? 4 : 3) : 0;
     return MZ_OK;
 }
 

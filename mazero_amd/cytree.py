@@ -459,6 +459,13 @@ class Tree_batch:
         check(self._lib, self._lib.mz_fused_kernel(self._h, buf, len(buf)), "fused_kernel")
         return buf.value.decode()
 
+    def fused_waves(self) -> int:
+        """Wavefronts per workgroup of this handle's k_chain3 launches (4 with the draw wave, else
+        3; 0 when it launches another kernel): include/mzdriver.h mz_fused_waves."""
+        n = C.c_int(0)
+        check(self._lib, self._lib.mz_fused_waves(self._h, C.byref(n)), "fused_waves")
+        return int(n.value)
+
     def synchronize(self):
         self._sync_stream()
         check(self._lib, self._lib.mz_synchronize(self._h), "synchronize")
