@@ -16,6 +16,8 @@
  * Integer and index results are exact; the float64 probabilities are the reference's own
  * operation sequence (Python sum, numpy cumsum, IEEE division), so they are bit-identical too.
  * The entropies use the device log and are within 1e-12 (relative) of scipy / numpy.
+ * The reanalyze batch's value / reward targets and normalised advantages (the last section) follow
+ * the same rule and are bit-identical to the reference's numpy arithmetic.
  *
  * Exported only by the product library (mazero_amd/_build/libmzmcts.so); device memory only.
  */
@@ -75,6 +77,72 @@ enum mz_marginal_mode {
  * legal_stride), required for ARGMAX, ignored by GIVEN. */
 int mz_marginal_policy(mz_batch *b, const int32_t *marginal, int64_t marginal_stride, const int32_t *legal,
                        int64_t legal_stride, int mode, int32_t *action_io, double *prob_io, double *entropy_out);
+
+/* ---- reanalyze batch targets (core/reanalyze_worker.py:376-489, make_batch) ------------------
+ *
+ * The two entry points below take a tree handle OR a stream: with b != NULL the launch goes to the
+ * handle's stream (ordered after its search, like the consumers above; `stream` is ignored); with
+ * b == NULL it goes to `stream` (a hipStream_t, NULL = the default stream) on the current device --
+ * the paths that run no search (NON_RE, use_pred_value) have no handle. */
+
+enum mz_value_mode {
+    MZ_VALUE_RE = 0,     /* _prepare_reward_value_re, reanalyze_worker.py:137-157 */
+    MZ_VALUE_NON_RE = 1, /* _prepare_reward_value_non_re, reanalyze_worker.py:186-204 */
+};
+
+/* The n-step value targets and the reward targets, one lane per row.  Row j = g * (U + 1) + k is
+ * unroll step k of trajectory g, current = pos[g] + k; the call covers rows [row0, row0 + n) of the
+ * G * (U + 1) rows (a rank's share), and value / td_pow / out_* are indexed by j - row0.
+ *   value      float32 [n]   RE: the agent-0 search's root values (reanalyze_worker.py:121-130) or
+ *                            the network's predicted values (:132-133); unused by NON_RE (may be NULL)
+ *   td_pow     float64 [n]   RE: np.power(discount, td_steps_lst) (:138), computed on the host by
+ *                            exactly that expression (numpy's array power is not libm's pow on
+ *                            every host, so the device does not recompute it); unused by NON_RE
+ *   td         int32 [G]     td steps of each trajectory (after the clip of :82-84; NON_RE: all equal)
+ *   pos, traj_len, reward_len  int32 [G]  state_index, len(game), len(game.rewards) >= traj_len
+ *   rewards    [G, L]        game.rewards, rows padded to L; float32 when rewards_f32 else float64
+ *   stored     [G, L]        NON_RE: game.root_values or game.pred_values (:191-194), padded;
+ *                            float32 when stored_f32 else float64; unused by RE (may be NULL)
+ *   dpow float64 [td_max], dpow32 float32 [td_max]   discount ** i as Python computes it, and that
+ *                            cast to float32; td[g] <= td_max
+ * RE:      v = (double)value[j] * td_pow[j];  v = v * (double)(current + td[g] < traj_len[g]);
+ * NON_RE:  v = stored[g][current + td[g]] if current + td[g] < traj_len[g], else Python's int 0;
+ * both:    for i in 0 .. min(current + td[g], reward_len[g]) - current - 1:  v += term(i), in order.
+ * term(i) = reward * discount ** i under numpy 2 scalar promotion: a float64 reward gives the
+ * float64 product with dpow[i], a float32 reward the float32 product with dpow32[i].  RE accumulates
+ * in float64; NON_RE accumulates in float32 while rewards are float32 and the start is a float32
+ * stored value or the int 0, in float64 otherwise.
+ *   out_value[j - row0]  = v                    if current < traj_len[g] else 0   (float64 [n])
+ *   out_reward[j - row0] = rewards[g][current]  if current < traj_len[g] else 0   (float64 [n])
+ * Every index read from td / pos / traj_len / reward_len is clamped to the buffers' extents. */
+int mz_value_targets(mz_batch *b, void *stream, int mode, int64_t row0, int n, int G, int U, const float *value,
+                     const double *td_pow, const int32_t *td, const int32_t *pos, const int32_t *traj_len,
+                     const int32_t *reward_len, const void *rewards, int rewards_f32, const void *stored,
+                     int stored_f32, int64_t L, const double *dpow, const float *dpow32, int td_max,
+                     double *out_value, double *out_reward);
+
+/* numpy's float64 sum (np.add.reduce) of n contiguous elements as a plan (host only: no device
+ * call).  numpy sums chunks of 8192 elements (its default buffer size) one after the other, in
+ * order, each chunk by its pairwise recursion (above 128 elements: split at n2 = n / 2,
+ * n2 -= n2 % 8, sum(left) + sum(right)).  Chunks and recursion are walked once: leaf l covers [starts[l], starts[l + 1]) (starts[num_leaves] = n; at most 128
+ * elements, each start a multiple of 8), and ops is the recursion in postfix order: 0 pushes the
+ * next leaf's sum, 1 replaces the two topmost sums by their sum.  A leaf of fewer than 8 elements
+ * is a serial sum from 0.0; otherwise eight accumulators r[i] over the elements i mod 8 of the
+ * whole groups of 8, combined ((r0+r1)+(r2+r3))+((r4+r5)+(r6+r7)), then the n % 8 tail in order.
+ * starts holds cap + 1 entries, ops 2 * cap; 1 <= n <= 65536 needs cap <= 1024. */
+int mz_pairwise_plan(int n, int32_t *starts, int32_t *ops, int cap, int32_t *num_leaves, int32_t *num_ops);
+
+/* Step (6) of make_batch (reanalyze_worker.py:466-473) over the whole batch, one workgroup:
+ *   adv = (double)q - (double)pred;  mean = np.nanmean, std = np.nanstd over the entries with
+ *   mask != 0 (and adv not NaN);  adv_out = (adv - mean) / (std + 1e-5), 0 where mask == 0.
+ * numpy's own evaluation, bit for bit: mean = pairwise_sum(where(valid, adv, 0)) / cnt,
+ * d = where(valid, adv - mean, 0), std = sqrt(pairwise_sum(d * d) / cnt), the pairwise sums by the
+ * plan above.  cnt == 0 gives adv_out all zero and NaN statistics.
+ *   q, pred float32 [n]; mask uint8 [n]; adv_out float64 [n]; stats_out float64 [2] = mean, std.
+ * 1 <= n <= 65536 (MZ_ERR_UNSUPPORTED above).  The plan of each n is built and uploaded on first
+ * use and kept: make the first call for an n outside any stream capture. */
+int mz_normalize_advantage(mz_batch *b, void *stream, const float *q, const float *pred, const uint8_t *mask, int n,
+                           double *adv_out, double *stats_out);
 
 #ifdef __cplusplus
 }

@@ -137,7 +137,14 @@ CONSUME_SIGNATURES = {
     "mz_select_actions": (_i, [_p, _p, _p, _p, _i, C.c_double, _i, _p, _p, _p, _p]),
     "mz_eps_greedy": (_i, [_p, _p, _i64, _f, _p, _p, _p]),
     "mz_marginal_policy": (_i, [_p, _p, _i64, _p, _i64, _i, _p, _p, _p]),
+    # reanalyze batch targets: (handle or NULL, stream, ...)
+    "mz_value_targets": (_i, [_p, _p, _i, _i64, _i, _i, _i, _p, _p, _p, _p, _p, _p, _p, _i, _p, _i, _i64, _p, _p, _i,
+                              _p, _p]),
+    "mz_pairwise_plan": (_i, [_i, C.POINTER(C.c_int32), C.POINTER(C.c_int32), _i, C.POINTER(C.c_int32),
+                              C.POINTER(C.c_int32)]),
+    "mz_normalize_advantage": (_i, [_p, _p, _p, _p, _p, _i, _p, _p]),
 }
+MZ_VALUE_RE, MZ_VALUE_NON_RE = 0, 1
 CONSUME_EXPORTS = sorted(CONSUME_SIGNATURES)
 
 

@@ -27,7 +27,7 @@ from typing import List, NamedTuple, Optional, Tuple
 import numpy as np
 import torch
 
-from ._capi import MZ_MARGINAL_ARGMAX, MZ_MARGINAL_GIVEN, check
+from ._capi import MZ_MARGINAL_ARGMAX, MZ_MARGINAL_GIVEN, MZ_VALUE_NON_RE, MZ_VALUE_RE, check
 from .mcts_sampled import DeviceSearchOutput
 
 
@@ -258,3 +258,197 @@ def reanalyze_policy_targets(mcts, model, network_output, legal_actions_lst, pol
         pv = pv.reshape(B, 1)
     return ReanalyzePolicy(current.reshape(B, 1, N), prob.to(torch.float32).reshape(B, 1),
                            torch.ones(B, 1, dtype=torch.float32, device=dev), masks, value0, value0, pv)
+
+
+# ------------------------------------------------------------------------------------------------
+# reanalyze batch targets: value, reward, advantage (core/reanalyze_worker.py:376-489, make_batch)
+# ------------------------------------------------------------------------------------------------
+def _stream_args(tb, dev):
+    """(library, handle, stream) of a launch: the tree handle's stream, or torch's current one."""
+    if tb is not None:
+        return tb._lib, tb._h, None
+    from ._lib import load
+    from .cytree import _raw_stream_of
+
+    return load(), None, C.c_void_p(_raw_stream_of(dev.index if dev.index is not None else torch.cuda.current_device()))
+
+
+def _padded_rows(rows, what: str) -> Tuple[np.ndarray, np.ndarray]:
+    """Per-trajectory sequences -> ([G, L] array of their common float dtype, lengths int32 [G]).
+    float32 stays float32 (numpy's scalar promotion depends on it); everything else is float64."""
+    arrs = [np.asarray(r).reshape(-1) for r in rows]
+    kinds = {a.dtype for a in arrs if a.size}
+    dtype = np.float32 if kinds == {np.dtype(np.float32)} else np.float64
+    if dtype is np.float64 and np.dtype(np.float32) in kinds:
+        raise ValueError(f"{what}: float32 and other dtypes mixed across trajectories")
+    lens = np.array([a.shape[0] for a in arrs], np.int32)
+    out = np.zeros((len(arrs), max(1, int(lens.max(initial=0)))), dtype)
+    for g, a in enumerate(arrs):
+        out[g, : lens[g]] = a
+    return out, lens
+
+
+class _TargetInputs(NamedTuple):
+    G: int
+    U: int
+    td: np.ndarray
+    td_max: int
+    dev_args: tuple  # td, pos, traj_len, reward_len, rewards, dpow, dpow32 (device tensors)
+    rewards_f32: bool
+    L: int
+
+
+def _target_inputs(rewards, pos, traj_len, td_steps, discount, num_unroll_steps, td_max, dev) -> _TargetInputs:
+    rew, rlen = _padded_rows(rewards, "rewards")
+    G, L = rew.shape
+    pos = np.asarray(pos, np.int64).reshape(-1)
+    tl = np.asarray(traj_len, np.int64).reshape(-1)
+    td = np.asarray(td_steps, np.int64).reshape(-1)
+    if td.shape[0] == 1 and G > 1:
+        td = np.repeat(td, G)
+    if not (pos.shape[0] == tl.shape[0] == td.shape[0] == G):
+        raise ValueError(f"rewards, pos, traj_len, td_steps must describe the same {G} trajectories")
+    if (rlen < tl).any():
+        raise ValueError("reward_len < traj_len: a trajectory holds fewer rewards than steps")
+    if (pos < 0).any() or (tl < 0).any() or (td < 0).any():
+        raise ValueError("pos, traj_len and td_steps must be >= 0")
+    td_max = int(td.max()) if td_max is None else int(td_max)
+    td_max = max(td_max, 1)
+    if (td > td_max).any():
+        raise ValueError(f"td_steps above td_max = {td_max}")
+    dpow = np.array([float(discount) ** i for i in range(td_max)], np.float64)  # Python's own power
+    t = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)  # noqa: E731
+    dev_args = (t(td.astype(np.int32)), t(pos.astype(np.int32)), t(tl.astype(np.int32)), t(rlen), t(rew), t(dpow),
+                t(dpow.astype(np.float32)))
+    return _TargetInputs(G, int(num_unroll_steps), td, td_max, dev_args, rew.dtype == np.float32, L)
+
+
+def _launch_value_targets(tb, dev, mode, ti: _TargetInputs, lo, hi, value, td_pow, stored, stored_f32):
+    n = hi - lo
+    out_v = torch.empty(n, dtype=torch.float64, device=dev)
+    out_r = torch.empty(n, dtype=torch.float64, device=dev)
+    td, pos, tl, rlen, rew, dpow, dpow32 = ti.dev_args
+    lib, h, stream = _stream_args(tb, dev)
+    with torch.cuda.device(dev):
+        check(lib, lib.mz_value_targets(h, stream, int(mode), int(lo), int(n), ti.G, ti.U, _p(value), _p(td_pow),
+                                        _p(td), _p(pos), _p(tl), _p(rlen), _p(rew), int(ti.rewards_f32), _p(stored),
+                                        int(stored_f32), ti.L, _p(dpow), _p(dpow32), ti.td_max, _p(out_v), _p(out_r)),
+              "value_targets")
+    return out_r, out_v
+
+
+def _rows_of(rows, total):
+    lo, hi = (0, total) if rows is None else (int(rows[0]), int(rows[1]))
+    if not 0 <= lo < hi <= total:
+        raise ValueError(f"rows {rows} outside the batch's {total} rows")
+    return lo, hi
+
+
+def reanalyze_value_targets(mcts, model, network_output, legal_actions_lst, *, rewards, pos, traj_len, td_steps,
+                            discount: float, num_unroll_steps: int, td_max: Optional[int] = None,
+                            use_root_value: bool = True, use_pred_value: bool = False, rows=None, device=None
+                            ) -> Tuple[torch.Tensor, torch.Tensor]:
+    """`_prepare_reward_value_re` after the initial inference (reanalyze_worker.py:116-164) ->
+    (batch_rewards, batch_values), float64 [G, U+1] device tensors.
+
+    `network_output` is the inference on the bootstrap observations of the G * (U+1) rows (row
+    j = g * (U+1) + k, :90-103) and `legal_actions_lst` their legal actions.  With `use_root_value`
+    the agent-0 search of :121-129 runs here (add_noise=True, sampled_tau=1.0, factor=None;
+    `mcts.np_random` is consumed as the reference consumes `self.np_random`) and its
+    `DeviceSearchOutput.value` feeds the kernel in the search's stream, without a host copy; with
+    `use_pred_value` the kernel takes `network_output.value` (mcts, model, legal_actions_lst unused).
+
+    rewards: per trajectory, `game.rewards` (all float64 / Python floats, or all float32: the
+    reference's arithmetic depends on it, include/mzconsume.h); pos, traj_len: `game_pos_lst`,
+    `len(game)`; td_steps: per trajectory, after the clip of :82-84 (`td_max` defaults to their
+    maximum; pass config.td_steps to keep one table size).
+
+    rows = (lo, hi): `network_output` holds rows [lo, hi) only (a rank's share, with `mcts` built
+    for that root shard); the result is then flat, float64 [hi - lo] each."""
+    U = int(num_unroll_steps)
+    hidden = network_output.hidden_state
+    dev = hidden.device if isinstance(hidden, torch.Tensor) and hidden.is_cuda else torch.device(device or "cuda")
+    ti = _target_inputs(rewards, pos, traj_len, td_steps, discount, U, td_max, dev)
+    total = ti.G * (U + 1)
+    lo, hi = _rows_of(rows, total)
+    n = hi - lo
+    # :138 on the whole batch's list, exactly the reference's expression (numpy's array power)
+    td_steps_lst = [np.intc(x) for x in np.repeat(ti.td, U + 1)]
+    td_pow = torch.from_numpy(np.ascontiguousarray(np.power(discount, td_steps_lst)[lo:hi], dtype=np.float64)).to(dev)
+    tb = None
+    if use_root_value:
+        legal_np = np.asarray(legal_actions_lst)
+        out = mcts.batch_search_device(model, network_output, 0, None, legal_np.shape[1], legal_np, device,
+                                       add_noise=True, sampled_tau=1.0)
+        tb = _tree(out)
+        value = out.value.reshape(-1)
+    elif use_pred_value:
+        value = torch.as_tensor(network_output.value).to(device=dev, dtype=torch.float32).reshape(-1).contiguous()
+    else:
+        raise NotImplementedError  # as the reference, :134-135
+    if value.shape[0] != n:
+        raise ValueError(f"{value.shape[0]} values for {n} rows")
+    r, v = _launch_value_targets(tb, dev, MZ_VALUE_RE, ti, lo, hi, value, td_pow, None, False)
+    return (r, v) if rows is not None else (r.reshape(ti.G, U + 1), v.reshape(ti.G, U + 1))
+
+
+def value_targets_non_re(rewards, stored, pos, traj_len, *, td_steps: int, discount: float, num_unroll_steps: int,
+                         rows=None, device=None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """`_prepare_reward_value_non_re` (reanalyze_worker.py:166-210) -> (batch_rewards,
+    batch_values), float64 [G, U+1] device tensors, in torch's current stream.  stored: per
+    trajectory, `game.root_values` (use_root_value) or `game.pred_values` (use_pred_value), all
+    float32 or all float64 like `rewards`; td_steps: config.td_steps."""
+    dev = torch.device(device or "cuda")
+    if dev.index is None:
+        dev = torch.device("cuda", torch.cuda.current_device())
+    U = int(num_unroll_steps)
+    ti = _target_inputs(rewards, pos, traj_len, [int(td_steps)], discount, U, int(td_steps), dev)
+    st, slen = _padded_rows(stored, "stored")
+    if st.shape[0] != ti.G or (slen < np.asarray(traj_len).reshape(-1)).any():
+        raise ValueError("stored values must cover every step of every trajectory")
+    st_full = np.zeros((ti.G, ti.L), st.dtype)  # the rewards' row stride
+    w = min(ti.L, st.shape[1])
+    st_full[:, :w] = st[:, :w]
+    lo, hi = _rows_of(rows, ti.G * (U + 1))
+    r, v = _launch_value_targets(None, dev, MZ_VALUE_NON_RE, ti, lo, hi, None, None,
+                                 torch.from_numpy(st_full).to(dev), st.dtype == np.float32)
+    return (r, v) if rows is not None else (r.reshape(ti.G, U + 1), v.reshape(ti.G, U + 1))
+
+
+def pairwise_plan(n: int, lib=None) -> Tuple[np.ndarray, np.ndarray]:
+    """numpy's float64 pairwise sum of n elements as (leaf starts [leaves + 1], postfix ops), the
+    plan mz_normalize_advantage sums by (include/mzconsume.h mz_pairwise_plan; no device call)."""
+    if lib is None:
+        from ._lib import load
+
+        lib = load()
+    cap = 1024
+    starts = (C.c_int32 * (cap + 1))()
+    ops = (C.c_int32 * (2 * cap))()
+    nl, nops = C.c_int32(), C.c_int32()
+    check(lib, lib.mz_pairwise_plan(int(n), starts, ops, cap, C.byref(nl), C.byref(nops)), "pairwise_plan")
+    return np.array(starts[: nl.value + 1], np.int32), np.array(ops[: nops.value], np.int32)
+
+
+def normalize_advantage(q: torch.Tensor, pred: torch.Tensor, mask: torch.Tensor, out: DeviceSearchOutput = None
+                        ) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Step (6) of make_batch (reanalyze_worker.py:466-473) on the gathered batch: q =
+    batch_sampled_qvalues, pred = batch_root_pred_values (float32), mask = batch_sampled_masks ->
+    (batch_sampled_adv float64, q's shape; float64 [2] = adv_mean, adv_std), numpy's nanmean /
+    nanstd bit for bit.  The statistics span the whole batch: gather the ranks' rows first (this
+    call is not sharded).  Runs in torch's current stream, or in `out`'s tree's when given.  At
+    most 65,536 entries; the first call for a size must be outside any graph capture."""
+    dev = q.device
+    qf = q.to(torch.float32).reshape(-1).contiguous()
+    pf = torch.as_tensor(pred).to(device=dev, dtype=torch.float32).reshape(-1).contiguous()
+    mf = torch.as_tensor(mask).to(device=dev).reshape(-1).ne(0).to(torch.uint8).contiguous()
+    n = qf.shape[0]
+    if pf.shape[0] != n or mf.shape[0] != n:
+        raise ValueError("q, pred and mask must have the same number of entries")
+    adv = torch.empty(n, dtype=torch.float64, device=dev)
+    stats = torch.empty(2, dtype=torch.float64, device=dev)
+    lib, h, stream = _stream_args(_tree(out) if out is not None else None, dev)
+    with torch.cuda.device(dev):
+        check(lib, lib.mz_normalize_advantage(h, stream, _p(qf), _p(pf), _p(mf), int(n), _p(adv), _p(stats)),
+              "normalize_advantage")
+    return adv.reshape(q.shape), stats

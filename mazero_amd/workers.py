@@ -176,7 +176,8 @@ class SelfPlayShard(_Shard):
 
 class ReanalyzeShard(_Shard):
     """One rank of process-per-GPU reanalysis: the policy targets of `_prepare_policy_re`
-    (reanalyze_worker.py:212-366) for this rank's share of a batch's B·(K+1) roots, with the target
+    (reanalyze_worker.py:212-366) and the value / reward targets of `_prepare_reward_value_re`
+    (:51-164) for this rank's share of a batch's B·(K+1) roots, with the target
     weights refreshed by the target-model-interval rule (reanalyze_worker.py:663-669; build the
     broadcaster with checkpoint_interval = config.target_model_interval)."""
 
@@ -194,3 +195,28 @@ class ReanalyzeShard(_Shard):
         out["model_index"] = idx
         out["lo"] = self.lo
         return out
+
+    def value_targets(self, obs, legal, *, rewards, pos, traj_len, td_steps, num_unroll_steps: int,
+                      discount: Optional[float] = None, td_max: Optional[int] = None, use_root_value: bool = True
+                      ) -> dict:
+        """The value and reward targets of `_prepare_reward_value_re` (reanalyze_worker.py:51-164)
+        for this rank's rows [lo, hi) of the batch's G·(U+1) rows (`total_roots`).  obs / legal: the
+        rank's rows of the bootstrap observations and legal actions (:86-103); rewards, pos,
+        traj_len, td_steps: the whole batch's G trajectories (a few numbers each: every rank holds
+        them).  Rows are independent, so the result equals rows [lo, hi) of the unsharded call.
+        `use_root_value=False` is the reference's use_pred_value.  The advantage normalisation of
+        make_batch's step (6) needs the whole batch: gather the ranks' rows, then call
+        `consume.normalize_advantage` once."""
+        if len(pos) * (int(num_unroll_steps) + 1) != self.total:
+            raise ValueError(f"{len(pos)} trajectories x {int(num_unroll_steps) + 1} rows != {self.total} roots")
+        idx = self._sync()
+        net_out = self._initial_inference(obs)
+        mcts = self.make_mcts(self.config, self.np_random, self.root_shard)
+        from .consume import reanalyze_value_targets
+
+        r, v = reanalyze_value_targets(
+            mcts, self.model, net_out, legal, rewards=rewards, pos=pos, traj_len=traj_len, td_steps=td_steps,
+            discount=self.config.discount if discount is None else discount, num_unroll_steps=num_unroll_steps,
+            td_max=td_max, use_root_value=use_root_value, use_pred_value=not use_root_value,
+            rows=(self.lo, self.hi), device=self.device)
+        return dict(batch_rewards=_to_np(r), batch_values=_to_np(v), model_index=idx, lo=self.lo)
