@@ -9,6 +9,10 @@ reference runs it.
 Reported, as one JSON line:
 - `device`: mazero_amd.mcts_sampled.SampledMCTS. The tree, pool and glue are on the GPU, and
   the search loop is captured in a HIP graph after the first search of each configuration.
+- `device_fused_transforms`: `device` with `fused_transforms=True`: the value and reward heads'
+  inverse support transforms of every simulation in one launch (mz_inverse_transform) instead of the
+  model's torch ops. Same network and seeds; `actions_equal_device` says whether one environment
+  step's sampled actions and visit counts equal the `device` loop's.
 - `device_eager`: the same driver without graphs.
 - `selfplay_step_host_consumers` / `selfplay_step_device_consumers`: a whole self-play step with
   its per-root decisions (select_action, epsilon-greedy, recorded policy probability,
@@ -101,6 +105,15 @@ def main():
             "unit": "simulations/s", "network": "MuZeroShapedNet (MLP heads, random init, autocast)"}
     t = timed(SampledMCTS(cfg, np.random.RandomState(0), use_graph=True), args.steps, 2, marks=True)
     line["device"] = {"value": round(sims_per_step / t, 1), "ms_per_step": round(t * 1e3, 3)}
+    # the same loop with the heads' inverse transforms in one launch (mz_inverse_transform): same
+    # network, same seeds, so the searches and the actions taken from them must be the same
+    t = timed(SampledMCTS(cfg, np.random.RandomState(0), use_graph=True, fused_transforms=True), args.steps, 2)
+    a = env_step(SampledMCTS(cfg, np.random.RandomState(5), use_graph=True), 0)
+    b = env_step(SampledMCTS(cfg, np.random.RandomState(5), use_graph=True, fused_transforms=True), 0)
+    same_actions = all(np.array_equal(x, y) for x, y in zip(a.sampled_actions, b.sampled_actions)) and \
+        all(np.array_equal(x, y) for x, y in zip(a.sampled_visit_count, b.sampled_visit_count))
+    line["device_fused_transforms"] = {"value": round(sims_per_step / t, 1), "ms_per_step": round(t * 1e3, 3),
+                                       "actions_equal_device": bool(same_actions)}
     if args.device_only:
         line["steps"] = args.steps
         print(json.dumps(line), flush=True)

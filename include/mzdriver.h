@@ -130,6 +130,30 @@ int mz_root_glue_wide(mz_batch *b, const void *logits, int dtype, int64_t row_st
 int mz_joint_action_wide(mz_batch *b, const void *pred_logits, int dtype, int num_agents, int current_agent,
                          const int32_t *factor, int factor_cols, const int32_t *actions, int64_t *joint_out);
 
+/* Inverse support transform of the value and the reward head of one simulation: what
+ * MAMuZeroNet.recurrent_inference applies to the two heads' logits in eval mode
+ * (config/smac/model.py:562-572; core/config.py:430-499: softmax, _inv_phi, _inv_h), both heads in
+ * one launch, written as the float32 [n] `rewards` / `values` inputs of mz_expand_backup_select.
+ * The results are bit-identical to the torch chain on the same device under autocast (softmax in
+ * float32, support * p, sum over the support, then _inv_h one float32 operation per Python operator):
+ * the reduction orders of torch's softmax and sum kernels are restated (mazero_amd/csrc/mzdriver.hip).
+ * `stage` says how much of the chain the call computes, i.e. what the inputs hold:
+ *   MZ_INV_LOGITS       [n, S] logits, MZ_DT_F32 or MZ_DT_F16 (read as float, as autocast's softmax does)
+ *   MZ_INV_PROBS        [n, S] float32 probabilities (the softmax's output)
+ *   MZ_INV_EXPECTATION  [n]    float32, the output of _inv_phi (the sum over the support)
+ * S = hi - lo + 1 is the size of the head's support lo..hi; row i starts at element i * stride.
+ * LOGITS and PROBS hold one support element per lane: 1 <= S <= 64, else MZ_ERR_UNSUPPORTED;
+ * EXPECTATION takes any S.  A head whose input and output are both NULL is left out.
+ * b != NULL: the launch goes to the handle's stream and `stream` is ignored; b == NULL: to `stream`
+ * (a hipStream_t, NULL = the default stream) on the current device.  Nothing is allocated or
+ * uploaded by the call, so it can be captured in a graph. */
+enum mz_inv_stage { MZ_INV_LOGITS = 0, MZ_INV_PROBS = 1, MZ_INV_EXPECTATION = 2 };
+
+int mz_inverse_transform(mz_batch *b, void *stream, int stage, int n,
+                         const void *value_in, int value_dtype, int64_t value_stride, int value_lo, int value_hi,
+                         const void *reward_in, int reward_dtype, int64_t reward_stride, int reward_lo, int reward_hi,
+                         float *value_out, float *reward_out);
+
 /* The base-case blocks the wide kernels sum a row of n elements in (1 <= n <= 255), as the launchers
  * compute them: starts[3], lens[3] (unused entries 0) and their count.  Host only, no device call;
  * for the tests that check the plan against np.sum. */

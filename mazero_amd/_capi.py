@@ -108,6 +108,7 @@ _i64 = C.c_int64
 
 # include/mzdriver.h (device glue of the driver loop; exported by the product library only)
 MZ_DT_F32, MZ_DT_F16 = 0, 1
+MZ_INV_LOGITS, MZ_INV_PROBS, MZ_INV_EXPECTATION = 0, 1, 2  # enum mz_inv_stage
 DRIVER_SIGNATURES = {
     "mz_reseed": (_i, [_p, C.c_uint32]),
     "mz_state_changed": (_i, [_p]),
@@ -118,6 +119,8 @@ DRIVER_SIGNATURES = {
     "mz_policy_glue_wide": (_i, [_p, _p, _i, _i64, _i64, C.c_double, _p, _p]),
     "mz_root_glue_wide": (_i, [_p, _p, _i, _i64, _i64, _p, _i64, _p, C.c_double, C.c_double, _p, _p, _p]),
     "mz_joint_action_wide": (_i, [_p, _p, _i, _i, _i, _p, _i, _p, _p]),
+    # (handle or NULL, stream, stage, n, value head: in, dtype, stride, lo, hi; reward head likewise; outputs)
+    "mz_inverse_transform": (_i, [_p, _p, _i, _i, _p, _i, _i64, _i, _i, _p, _i, _i64, _i, _i, _p, _p]),
     "mz_wide_sum_plan": (_i, [_i, C.POINTER(_i), C.POINTER(_i), C.POINTER(_i)]),
     "mz_graph_census": (_i, [_p, C.POINTER(_i), C.POINTER(_i)]),
     "mz_fused_kernel": (_i, [_p, C.c_char_p, _i]),

@@ -537,6 +537,101 @@ __global__ __launch_bounds__(kWave) void k_joint_action_wide(const void *pred, i
     }
 }
 
+// ------------------------------------------------------------------------------------------------
+// Inverse support transform of the value and reward heads (core/config.py:430-499 after
+// config/smac/model.py:562-572): softmax -> _inv_phi -> _inv_h.  The target is not numpy but the
+// torch chain on this device (mazero_amd.nets.inverse_support_transform under autocast), restated
+// from the kernels torch launches for it:
+//   softmax   softmax_warp_forward (ATen PersistentSoftmax.cuh): next_pow2(S) lanes, one element per
+//             lane for S <= 64, pad lanes at -inf; max `a < b ? b : a` and the sum as xor butterflies
+//             from width / 2 down to 1, every lane keeping its own result (a NaN does not spread
+//             through the max, so lanes may hold different maxima; the sum spreads it); ::exp;
+//             NaN in every element when the sum is 0
+//   mul       float(support) * p, one f32 multiply
+//   sum       ATen Reduce.cuh for fewer than 128 inputs per output: block width bw = last_pow2(S);
+//             thread x adds elements x and x + bw to accumulators 0 and 1 of four that start at 0,
+//             joins them ((v0 + v1) + v2) + v3, then lane x takes lane x + offset for offset = 1, 2,
+//             .. < bw; the row's sum is lane 0's
+//   _inv_h    one f32 kernel per Python operator, Python scalars cast to f32; a tensor divided by a
+//             Python scalar is multiplied by the scalar's reciprocal (double, cast to f32)
+// This translation unit is built without FMA contraction and with IEEE divide and sqrt.
+constexpr int kInvWaves = 4;  // waves per workgroup of k_inverse_rows
+constexpr int kInvLanes = 256;
+constexpr int kInvMaxGrid = 1 << 20;
+constexpr float kInvEps = (float)0.001;
+constexpr float kInv4Eps = (float)(4 * 0.001);
+// `/ (2 * epsilon)`: torch multiplies by the reciprocal, taken in double and then cast (500.0f; the
+// f32 reciprocal of f32(0.002) would be 499.99997f)
+constexpr float kInvHalfOverEps = (float)(1.0 / (2 * 0.001));
+
+struct InvHead {
+    const void *in;
+    float *out;
+    long long stride;  // elements between rows
+    int lo, S;         // the support is lo .. lo + S - 1
+    int f16;
+};
+
+__device__ __forceinline__ float torch_inv_h(float x) {
+    float a = fabsf(x) + 1.0f;
+    a = a + kInvEps;
+    a = kInv4Eps * a;
+    a = 1.0f + a;
+    a = sqrtf(a);  // (IEEE: -fhip-fp32-correctly-rounded-divide-sqrt)
+    a = a - 1.0f;
+    a = a * kInvHalfOverEps;
+    a = a * a;
+    a = a - 1.0f;
+    float out = (x < 0.f ? -1.0f : 1.0f) * a;
+    if (out != out) out = 0.f;
+    if (fabsf(out) < kInvEps) out = 0.f;
+    return out;
+}
+
+// One wave per (row, head), lane l holds support element l; blockIdx.y is the head.
+__global__ __launch_bounds__(kInvLanes) void k_inverse_rows(InvHead h0, InvHead h1, int n, int probs) {
+    const InvHead h = blockIdx.y ? h1 : h0;
+    const int l = threadIdx.x & (kWave - 1);
+    const int S = h.S;
+    int W = 1, bw = 1;  // next_pow2(S), last_pow2(S)
+    while (W < S) W <<= 1;
+    while (2 * bw <= S) bw <<= 1;
+    const bool on = l < S;
+    for (long long row = (long long)blockIdx.x * kInvWaves + (threadIdx.x >> 6); row < n;
+         row += (long long)gridDim.x * kInvWaves) {
+        float p;
+        if (probs) {
+            p = on ? static_cast<const float *>(h.in)[row * h.stride + l] : 0.f;
+        } else {
+            float x = -INFINITY;
+            if (on) x = h.f16 ? load_elem<true>(h.in, row * h.stride + l) : load_elem<false>(h.in, row * h.stride + l);
+            float m = x;
+            for (int o = W >> 1; o > 0; o >>= 1) {
+                const float b = __shfl_xor(m, o, kWave);
+                m = m < b ? b : m;
+            }
+            const float e = ::expf(x - m);
+            float s = 0.0f + e;
+            for (int o = W >> 1; o > 0; o >>= 1) s = s + __shfl_xor(s, o, kWave);
+            p = (s == 0.f) ? NAN : e / s;
+        }
+        const float q = on ? (float)(h.lo + l) * p : 0.f;
+        const float q2 = bw < kWave ? __shfl_down(q, bw, kWave) : 0.f;
+        const float v0 = 0.0f + q;
+        const float v1 = (l + bw < S) ? 0.0f + q2 : 0.0f;
+        float acc = ((v0 + v1) + 0.0f) + 0.0f;
+        for (int o = 1; o < bw; o <<= 1) acc = acc + __shfl_down(acc, o, kWave);
+        if (l == 0) h.out[row] = torch_inv_h(acc);
+    }
+}
+
+// MZ_INV_EXPECTATION: one lane per (row, head)
+__global__ __launch_bounds__(kInvLanes) void k_inverse_scalars(InvHead h0, InvHead h1, int n) {
+    const InvHead h = blockIdx.y ? h1 : h0;
+    for (long long i = (long long)blockIdx.x * kInvLanes + threadIdx.x; i < n; i += (long long)gridDim.x * kInvLanes)
+        h.out[i] = torch_inv_h(static_cast<const float *>(h.in)[i * h.stride]);
+}
+
 // the table of mz_set_half_exp_table per device (allocated once, never freed: captured graphs keep
 // its address)
 constexpr int kMaxDevices = 64;
@@ -763,6 +858,61 @@ int mz_joint_action_wide(mz_batch *b, const void *pred_logits, int dtype, int nu
                          const int32_t *factor, int factor_cols, const int32_t *actions, int64_t *joint_out) {
     return joint_action("mz_joint_action_wide", true, b, pred_logits, dtype, num_agents, current_agent, factor,
                         factor_cols, actions, joint_out);
+}
+
+int mz_inverse_transform(mz_batch *b, void *stream, int stage, int n, const void *value_in, int value_dtype,
+                         int64_t value_stride, int value_lo, int value_hi, const void *reward_in, int reward_dtype,
+                         int64_t reward_stride, int reward_lo, int reward_hi, float *value_out, float *reward_out) {
+    const char *fn = "mz_inverse_transform";
+    hipStream_t s = (hipStream_t)stream;
+    if (b) {  // the handle's device current, its stream
+        int B = 0, A = 0;
+        int rc = mz_internal_launch_info(b, &B, &A, &s);
+        if (rc) return rc;
+    }
+    if (stage != MZ_INV_LOGITS && stage != MZ_INV_PROBS && stage != MZ_INV_EXPECTATION)
+        return glue_fail(MZ_ERR_ARG, fn, "bad stage");
+    if (n < 0) return glue_fail(MZ_ERR_ARG, fn, "n must be >= 0");
+    InvHead heads[2] = {};
+    int nh = 0;
+    const struct {
+        const void *in;
+        int dtype;
+        int64_t stride;
+        int lo, hi;
+        float *out;
+    } args[2] = {{value_in, value_dtype, value_stride, value_lo, value_hi, value_out},
+                 {reward_in, reward_dtype, reward_stride, reward_lo, reward_hi, reward_out}};
+    for (const auto &a : args) {
+        if (!a.in && !a.out) continue;  // this head is not asked for
+        if (!a.in || !a.out) return glue_fail(MZ_ERR_ARG, fn, "a head needs both its input and its output");
+        if (a.dtype != MZ_DT_F32 && !(a.dtype == MZ_DT_F16 && stage == MZ_INV_LOGITS))
+            return glue_fail(MZ_ERR_ARG, fn, "bad dtype (logits: f32 or f16; probabilities and expectations: f32)");
+        if (a.hi < a.lo) return glue_fail(MZ_ERR_ARG, fn, "support hi < lo");
+        const int64_t S = (int64_t)a.hi - a.lo + 1;
+        if (stage != MZ_INV_EXPECTATION) {
+            if (S > kWave) return glue_fail(MZ_ERR_UNSUPPORTED, fn, "support size > 64 (one lane per support element)");
+            if (a.stride < S) return glue_fail(MZ_ERR_ARG, fn, "row stride below the support size");
+        } else if (a.stride < 1) {
+            return glue_fail(MZ_ERR_ARG, fn, "row stride must be >= 1");
+        }
+        heads[nh++] = InvHead{a.in, a.out, (long long)a.stride, a.lo, (int)(S > kWave ? 0 : S), a.dtype == MZ_DT_F16};
+    }
+    if (nh == 0) return glue_fail(MZ_ERR_ARG, fn, "both heads are null");
+    if (n == 0) return MZ_OK;
+    if (stage == MZ_INV_EXPECTATION) {
+        const long long blocks = ((long long)n + kInvLanes - 1) / kInvLanes;
+        hipLaunchKernelGGL(k_inverse_scalars, dim3((unsigned)(blocks < kInvMaxGrid ? blocks : kInvMaxGrid), nh),
+                           dim3(kInvLanes), 0, s, heads[0], heads[1], n);
+    } else {
+        const long long blocks = ((long long)n + kInvWaves - 1) / kInvWaves;
+        hipLaunchKernelGGL(k_inverse_rows, dim3((unsigned)(blocks < kInvMaxGrid ? blocks : kInvMaxGrid), nh),
+                           dim3(kInvLanes), 0, s, heads[0], heads[1], n, stage == MZ_INV_PROBS ? 1 : 0);
+    }
+    if (b) mz_internal_enqueued(b);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return mz_internal_fail(MZ_ERR_DEVICE, hipGetErrorString(e));
+    return MZ_OK;
 }
 
 int mz_wide_sum_plan(int n, int32_t *starts, int32_t *lens, int32_t *num_blocks) {

@@ -14,7 +14,9 @@ and the per-simulation glue stay on the device:
     policy softmax + beta                   mz_policy_glue (numpy float32/float16 arithmetic)
 
 (with `wide_actions`: mz_root_glue_wide, mz_joint_action_wide, mz_policy_glue_wide, for action spaces
-of 65..255)
+of 65..255; with `fused_transforms`: the inverse transforms of the value and reward heads are one
+mz_inverse_transform launch, torch's arithmetic on this device restated bit for bit, instead of the
+model's ~46 torch kernels)
 
 so a search has no host synchronisation between `prepare` and the final readback.  The root
 preprocessing (mcts_sampled.py:51-106) is split: the host draws from `np_random` (the Dirichlet
@@ -42,7 +44,7 @@ from typing import List, NamedTuple, Tuple
 import numpy as np
 import torch
 
-from ._capi import INT_FIELDS, MZ_DT_F16, MZ_DT_F32, check
+from ._capi import INT_FIELDS, MZ_DT_F16, MZ_DT_F32, MZ_INV_EXPECTATION, MZ_INV_LOGITS, MZ_INV_PROBS, check
 from .cytree import Tree_batch
 
 
@@ -115,8 +117,17 @@ class _SearchLoop:
     Every input is copied into the static buffers before a run, and the tree seed lives in device
     memory (mz_reseed), so replaying the graph is a new search."""
 
-    def __init__(self, tb, B, A, N, cur, hidden, dev, model, root_mode=None, wide=False):
+    def __init__(self, tb, B, A, N, cur, hidden, dev, model, root_mode=None, wide=False, fused=None):
         self.tb, self.B, self.A, self.N, self.cur, self.dev = tb, B, A, N, cur, dev
+        # fused = (value (lo, hi), reward (lo, hi)) or the string "identity": the inverse transforms of
+        # the two heads run as one mz_inverse_transform launch into inv_v / inv_r, which the tree call
+        # reads (SampledMCTS's fused_transforms); None: the model's own transforms
+        self.fused = fused
+        if fused is not None and fused != "identity":
+            self.inv_v = torch.empty(B, dtype=torch.float32, device=dev)
+            self.inv_r = torch.empty(B, dtype=torch.float32, device=dev)
+            # float32 supports of the EXPECTATION route (supports past 64 elements)
+            self.inv_support = [torch.arange(lo, hi + 1, dtype=torch.float32, device=dev) for lo, hi in fused]
         # the glue entry points this loop records: the _wide ones take A <= 255 (SampledMCTS's
         # wide_actions), the narrow ones refuse A > 64
         sfx = "_wide" if wide else ""
@@ -236,7 +247,19 @@ class _SearchLoop:
             check(lib, self.joint_action(h, ptr, dt, N, cur, C.c_void_p(self.fac.data_ptr()),
                                          self.fac.shape[1], C.c_void_p(act.data_ptr()),
                                          C.c_void_p(self.joint.data_ptr())), "joint_action")
-            next_h, reward, value, logits = SampledMCTS._recurrent(model, leaf, self.joint)  # :150-156
+            r32 = v32 = None
+            if self.fused is not None and getattr(model, "recurrent_inference_device", None) is None:
+                next_h, reward_logits = model.dynamics(leaf, self.joint)
+                logits, value_logits = model.prediction(next_h)
+                if self.fused == "identity":  # use_vectorization off: the heads' scalars, core/config.py:487-499
+                    reward, value = reward_logits, value_logits
+                elif self._inverse_transform(lib, h, value_logits, reward_logits):
+                    r32, v32 = self.inv_r, self.inv_v
+                else:
+                    reward = model.inverse_reward_transform(reward_logits)
+                    value = model.inverse_value_transform(value_logits)
+            else:
+                next_h, reward, value, logits = SampledMCTS._recurrent(model, leaf, self.joint)  # :150-156
             nh = next_h.reshape(B, -1)
             chain = K == 1
             if chain:
@@ -261,8 +284,9 @@ class _SearchLoop:
                                         logits.shape[1] * logits.shape[2], cur * A, float(tau),
                                         C.c_void_p(self.probs.data_ptr()), C.c_void_p(self.beta.data_ptr())),
                   "policy_glue")
-            r32 = reward.reshape(B).float()
-            v32 = value.reshape(B).float()
+            if r32 is None:
+                r32 = reward.reshape(B).float()
+                v32 = value.reshape(B).float()
             if s + 1 < S:
                 tb.expansion_backup_selection_device(s + 1, disc, K, r32, v32, self.probs, self.beta, c2, c1,
                                                      out=self.sel, pool=None if chain else self.pool,
@@ -275,6 +299,40 @@ class _SearchLoop:
                                                     readback_discount=disc)
             else:
                 tb.batch_expansion_and_backup(s + 1, disc, K, r32, v32, self.probs, self.beta)
+
+    def _inverse_transform(self, lib, h, value_logits, reward_logits) -> bool:
+        """inverse_value_transform / inverse_reward_transform of the two heads' logits (core/config.py:
+        487-499) as one mz_inverse_transform launch into inv_v / inv_r.  False: these logits are not
+        covered (the caller applies the model's own transforms): a dtype other than float32 / float16,
+        or half logits outside autocast, where torch rounds the softmax to half."""
+        B = self.B
+        heads = []
+        for t, (lo, hi) in zip((value_logits, reward_logits), self.fused):
+            if t.dtype not in (torch.float32, torch.float16):
+                return False
+            if t.dtype == torch.float16 and not torch.is_autocast_enabled("cuda"):
+                return False
+            if t.dim() != 2 or t.shape[0] != B or t.shape[1] != hi - lo + 1:
+                raise ValueError(f"fused_transforms: head logits of shape {tuple(t.shape)} for the support "
+                                 f"[{lo}, {hi}] of the config and {B} roots")
+            heads.append(t)
+        stage = FUSED_STAGE
+        if any(hi - lo + 1 > MAX_FUSED_SUPPORT for lo, hi in self.fused):
+            stage = MZ_INV_EXPECTATION  # (a support past one wave, the reference's default [-300, 300])
+        if stage == MZ_INV_LOGITS:
+            heads = [t if t.stride(1) == 1 else t.contiguous() for t in heads]
+        elif stage == MZ_INV_PROBS:
+            heads = [torch.softmax(t, dim=-1) for t in heads]
+        else:  # torch's softmax, multiply and sum; the kernel is _inv_h
+            heads = [torch.sum(sup * torch.softmax(t, dim=-1), dim=-1, keepdim=True)
+                     for t, sup in zip(heads, self.inv_support)]
+        (v, r), ((vlo, vhi), (rlo, rhi)) = heads, self.fused
+        check(lib, lib.mz_inverse_transform(h, None, stage, B,
+                                            C.c_void_p(v.data_ptr()), _dtype_code(v), v.stride(0), vlo, vhi,
+                                            C.c_void_p(r.data_ptr()), _dtype_code(r), r.stride(0), rlo, rhi,
+                                            C.c_void_p(self.inv_v.data_ptr()), C.c_void_p(self.inv_r.data_ptr())),
+              "inverse_transform")
+        return True
 
     def capture(self, model, cfg, eps, tau) -> bool:
         """Record the loop.  The recorded graph is checked before it is instantiated: under the HIP
@@ -392,14 +450,40 @@ def _storage_signature(model) -> tuple:
 
 MAX_GLUE_ACTIONS = 64  # include/mzdriver.h: the glue kernels hold one action per lane
 MAX_WIDE_ACTIONS = 255  # the _wide glue entry points: every action space the tree itself takes
+MAX_FUSED_SUPPORT = 64  # mz_inverse_transform's LOGITS / PROBS stages: one lane per support element
+# how much of softmax -> _inv_phi -> _inv_h the fused launch computes for supports of up to 64
+# elements; longer supports take MZ_INV_EXPECTATION behind torch's softmax and sum
+FUSED_STAGE = MZ_INV_LOGITS
+
+
+def _support_bounds(support) -> Tuple[int, int]:
+    """(lo, hi) of a DiscreteSupport-like object (`.min` / `.max`, core/config.py:247-255) or a pair."""
+    lo, hi = getattr(support, "min", None), getattr(support, "max", None)
+    if lo is None or hi is None or callable(lo) or callable(hi):  # (an array's min / max are methods)
+        lo, hi = support
+    lo, hi = int(lo), int(hi)
+    if hi < lo:
+        raise ValueError(f"support [{lo}, {hi}] is empty")
+    return lo, hi
 
 
 class SampledMCTS:
     """mcts_sampled.py:29-32.  `lib` selects the tree library (default: the MI355X product)."""
 
     def __init__(self, config, np_random: np.random.RandomState = None, *, lib=None, use_graph: bool = True,
-                 root_shard: Tuple[int, int, int] = None, device_root: bool = True, wide_actions: bool = None):
-        """`wide_actions`: run the driver glue through the _wide entry points (include/mzdriver.h), which
+                 root_shard: Tuple[int, int, int] = None, device_root: bool = True, wide_actions: bool = None,
+                 fused_transforms: bool = None):
+        """`fused_transforms`: compute the inverse value / reward transforms of every simulation
+        (core/config.py:487-499) with one mz_inverse_transform launch instead of the model's
+        `inverse_value_transform` / `inverse_reward_transform`; the search calls `model.dynamics` and
+        `model.prediction` itself.  The supports are `config.value_support` / `config.reward_support`
+        (objects with `.min` / `.max`, or (lo, hi) pairs); with `config.use_vectorization` False the
+        heads' scalars pass through.  None reads `config.fused_transforms` (False when the config has
+        none).  The results are those of the torch chain on the same device, bit for bit.  A model with
+        `recurrent_inference_device`, or head logits that are not float32 / autocast float16, keep the
+        model's own transforms.
+
+        `wide_actions`: run the driver glue through the _wide entry points (include/mzdriver.h), which
         take action spaces up to 255 instead of 64.  None reads `config.wide_actions` (False when the
         config has none), so a reference-style `SampledMCTS(config, np_random)` opts in through its
         config object.  Off by default: the refusal of A > 64 below is pinned by the test suite.
@@ -425,6 +509,16 @@ class SampledMCTS:
             raise RuntimeError(f"SampledMCTS: action_space_size {config.action_space_size} > {MAX_GLUE_ACTIONS} "
                                "(the device driver glue takes one lane per action; mazero_amd.cytree.Tree_batch "
                                "takes up to 255)")
+        if fused_transforms is None:
+            fused_transforms = getattr(config, "fused_transforms", False)
+        # None, "identity" (use_vectorization off) or the two heads' (lo, hi); part of the loop's key
+        self.fused_transforms = None
+        if fused_transforms:
+            if not getattr(config, "use_vectorization", True):
+                self.fused_transforms = "identity"
+            else:
+                self.fused_transforms = (_support_bounds(config.value_support),
+                                         _support_bounds(config.reward_support))
         self.np_random = np.random if np_random is None else np_random
         self._lib = lib
         if root_shard is not None:
@@ -592,7 +686,7 @@ class SampledMCTS:
             tb = self._tree(B, seed, dev)
             # the discount is a kernel argument of the recorded launches
             key = (threading.get_ident(), id(tb), id(model), N, cur, float(eps), float(sampled_tau), float(disc),
-                   tuple(hidden.shape), hidden.dtype, root_mode, self.wide_actions)
+                   tuple(hidden.shape), hidden.dtype, root_mode, self.wide_actions, self.fused_transforms)
             with _LOCK:
                 for k in [k for k, v in _LOOPS.items() if v.model_ref() is None]:
                     del _LOOPS[k]  # loops (graph, pool) of models that no longer exist
@@ -602,7 +696,7 @@ class SampledMCTS:
                 # addresses it was recorded with (re-homed weights, weights.FlatWeights, need a new one)
                 if st is None or st.model_ref() is not model or st.storage != sig or st.tb is not tb:
                     st = _LOOPS[key] = _SearchLoop(tb, B, A, N, cur, hidden, dev, model, root_mode,
-                                                   wide=self.wide_actions)
+                                                   wide=self.wide_actions, fused=self.fused_transforms)
                     st.storage = sig
                 _LOOPS.move_to_end(key)
                 while len(_LOOPS) > max(_MAX_LOOPS, 1):  # least recently used first

@@ -17,7 +17,7 @@ Weights are random (no checkpoints are available offline).
 from __future__ import annotations
 
 from dataclasses import dataclass
-from typing import List
+from typing import List, Tuple
 
 import numpy as np
 import torch
@@ -40,6 +40,12 @@ class SearchConfig:
     root_exploration_fraction: float = 0.25
     mcts_rho: float = 0.75
     mcts_lambda: float = 0.8
+    # the categorical supports of the value / reward heads as (min, max) (the reference holds
+    # DiscreteSupport objects, core/config.py:247-255) and whether the heads are categorical at all
+    # (core/config.py:487-499); read by SampledMCTS(fused_transforms=True)
+    value_support: Tuple[int, int] = (-5, 5)
+    reward_support: Tuple[int, int] = (-5, 5)
+    use_vectorization: bool = True
 
 
 def _mlp(inp: int, hidden: List[int], out: int) -> nn.Sequential:
@@ -56,9 +62,17 @@ def _mlp(inp: int, hidden: List[int], out: int) -> nn.Sequential:
 def inverse_support_transform(logits: torch.Tensor, lo: int, hi: int) -> torch.Tensor:
     """Categorical support → scalar: softmax, expectation over [lo, hi], then the inverse of
     h(x) = sign(x)(sqrt(|x|+1)-1) + 0.001x (core/config.py:430-499)."""
-    p = torch.softmax(logits, dim=-1)
-    support = torch.arange(lo, hi + 1, device=logits.device, dtype=torch.float32).expand(p.shape)
-    x = torch.sum(support * p, dim=-1, keepdim=True)
+    return inverse_h(support_expectation(torch.softmax(logits, dim=-1), lo, hi))
+
+
+def support_expectation(p: torch.Tensor, lo: int, hi: int) -> torch.Tensor:
+    """_inv_phi (core/config.py:463-475): the expectation of a distribution over the support [lo, hi]."""
+    support = torch.arange(lo, hi + 1, device=p.device, dtype=torch.float32).expand(p.shape)
+    return torch.sum(support * p, dim=-1, keepdim=True)
+
+
+def inverse_h(x: torch.Tensor) -> torch.Tensor:
+    """_inv_h (core/config.py:430-442)."""
     eps = 0.001
     sign = torch.ones(x.shape, dtype=torch.float32, device=x.device)
     sign[x < 0] = -1.0
