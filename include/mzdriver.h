@@ -142,7 +142,8 @@ int mz_joint_action_wide(mz_batch *b, const void *pred_logits, int dtype, int nu
  *   MZ_INV_PROBS        [n, S] float32 probabilities (the softmax's output)
  *   MZ_INV_EXPECTATION  [n]    float32, the output of _inv_phi (the sum over the support)
  * S = hi - lo + 1 is the size of the head's support lo..hi; row i starts at element i * stride.
- * LOGITS and PROBS hold one support element per lane: 1 <= S <= 64, else MZ_ERR_UNSUPPORTED;
+ * LOGITS and PROBS hold one support element per lane: 1 <= S <= 64, else MZ_ERR_UNSUPPORTED
+ * (mz_inverse_transform_wide below takes up to 1024);
  * EXPECTATION takes any S.  A head whose input and output are both NULL is left out.
  * b != NULL: the launch goes to the handle's stream and `stream` is ignored; b == NULL: to `stream`
  * (a hipStream_t, NULL = the default stream) on the current device.  Nothing is allocated or
@@ -153,6 +154,27 @@ int mz_inverse_transform(mz_batch *b, void *stream, int stage, int n,
                          const void *value_in, int value_dtype, int64_t value_stride, int value_lo, int value_hi,
                          const void *reward_in, int reward_dtype, int64_t reward_stride, int reward_lo, int reward_hi,
                          float *value_out, float *reward_out);
+
+/* mz_inverse_transform for supports of up to 1024 elements (the reference's default
+ * DiscreteSupport(-300, 300) has 601): the same arguments, stages and checks.  Heads of at most 64
+ * support elements run the kernel of mz_inverse_transform and give the same bytes; at LOGITS and
+ * PROBS a head of 65 .. 1024 elements runs k_inverse_rows_wide, which restates torch's softmax with
+ * several elements per lane and the vectorised path of its sum (mazero_amd/csrc/mzdriver.hip), again
+ * bit-identical to the torch chain on the same device under autocast.  That sum's order depends on
+ * the row index (the alignment of the row in torch's contiguous [n, S] product) and on n (the block
+ * width torch chooses), so `n` must be the row count of the torch call being replaced and row i its
+ * row i.  S > 1024 is MZ_ERR_UNSUPPORTED at LOGITS and PROBS (torch's softmax changes kernel there);
+ * EXPECTATION takes any S.  Nothing is allocated or uploaded by the call. */
+int mz_inverse_transform_wide(mz_batch *b, void *stream, int stage, int n,
+                              const void *value_in, int value_dtype, int64_t value_stride, int value_lo, int value_hi,
+                              const void *reward_in, int reward_dtype, int64_t reward_stride, int reward_lo, int reward_hi,
+                              float *value_out, float *reward_out);
+
+/* The plan of torch's sum over the last dimension of a contiguous float32 [n, S] tensor, as
+ * mz_inverse_transform_wide computes it per head (1 <= S <= 1024, n >= 1): whether the row is read as
+ * aligned vectors of 4 floats (S >= 128) and the block width, the number of threads that share a
+ * row.  Host only, no device call; for the tests that pin it against ReduceConfig's rule. */
+int mz_inverse_sum_plan(int S, int n, int *vectorized, int *block_width);
 
 /* The base-case blocks the wide kernels sum a row of n elements in (1 <= n <= 255), as the launchers
  * compute them: starts[3], lens[3] (unused entries 0) and their count.  Host only, no device call;

@@ -121,6 +121,8 @@ DRIVER_SIGNATURES = {
     "mz_joint_action_wide": (_i, [_p, _p, _i, _i, _i, _p, _i, _p, _p]),
     # (handle or NULL, stream, stage, n, value head: in, dtype, stride, lo, hi; reward head likewise; outputs)
     "mz_inverse_transform": (_i, [_p, _p, _i, _i, _p, _i, _i64, _i, _i, _p, _i, _i64, _i, _i, _p, _p]),
+    "mz_inverse_transform_wide": (_i, [_p, _p, _i, _i, _p, _i, _i64, _i, _i, _p, _i, _i64, _i, _i, _p, _p]),
+    "mz_inverse_sum_plan": (_i, [_i, _i, C.POINTER(_i), C.POINTER(_i)]),
     "mz_wide_sum_plan": (_i, [_i, C.POINTER(_i), C.POINTER(_i), C.POINTER(_i)]),
     "mz_graph_census": (_i, [_p, C.POINTER(_i), C.POINTER(_i)]),
     "mz_fused_kernel": (_i, [_p, C.c_char_p, _i]),

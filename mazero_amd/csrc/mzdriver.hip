@@ -632,6 +632,168 @@ __global__ __launch_bounds__(kInvLanes) void k_inverse_scalars(InvHead h0, InvHe
         h.out[i] = torch_inv_h(static_cast<const float *>(h.in)[i * h.stride]);
 }
 
+// ------------------------------------------------------------------------------------------------
+// The same chain for supports of 65 .. 1024 elements (the reference's default [-300, 300] is 601),
+// again restated from the kernels torch launches:
+//   softmax   softmax_warp_forward with W = next_pow2(S) / 64 elements per lane: lane l holds elements
+//             l + 64 it, elements past S at -inf; the lane's own maximum first, `m > x ? m : x` in it
+//             order (a NaN survives only as the last element), then the butterfly of k_inverse_rows
+//             (`m < b ? b : m`, 32 .. 1); ::exp; the lane's sum from 0.0f in it order, pad elements
+//             included, then the xor-add butterfly; NaN in every element when the sum is 0
+//   mul       float(support) * p, one f32 multiply, into a fresh contiguous [n, S] tensor
+//   sum       ATen Reduce.cuh over that tensor.  65 <= S < 128: block width 64, thread x adds elements x
+//             and x + 64 to accumulators 0 and 1 of four, as in k_inverse_rows.  S >= 128 ("vectorize
+//             along input"): the row is read as 16-byte-aligned vectors of 4 floats, so the order
+//             depends on the row's misalignment shift = (row * S) % 4: threads shift <= x < 4 first take
+//             row element x - shift into accumulator 0 (shift > 0), thread x then adds the aligned
+//             vectors x, x + bw, .. component i to accumulator i, threads x < 4 add the tail element to
+//             accumulator 0; join ((v0 + v1) + v2) + v3.  The block width bw (32 .. 256) follows from
+//             S and from the row count n (ReduceConfig::set_block_dimension; inverse_sum_plan below).
+//             Threads past 64 are folded through shared memory, t[x] += t[x + off] for off = bw / 2 ..
+//             64, then lane x takes lane x + off for off = 1, 2, .. < min(bw, 64).
+// One wave per (row, head) as in k_inverse_rows.  The products go through a row of LDS that only this
+// wave touches, placed at offset `shift` so that torch's vector loads are aligned LDS reads; lane l
+// plays torch's threads l, l + 64, l + 128, l + 192 in turn, so the shared-memory folds are adds
+// within the lane.  IT >= the elements per lane of either head (the elements stay in registers).
+// On the MI355X all of this held as derived from the installed torch's headers: bit-identical to the
+// torch chain for 16 support sizes from 65 to 1024, row counts on both sides of every block-width
+// switch, all four row alignments, f32 and f16 logits (tests/test_inverse_transform_wide.py); nothing
+// had to be corrected and no regime is refused.
+constexpr int kInvWideMax = 1024;            // softmax_warp_forward's limit
+constexpr int kInvWideRow = kInvWideMax + 4;  // + one vector: the row starts at offset shift <= 3
+
+struct InvPlan {
+    int vec;  // 1: "vectorize along input" (S >= 128)
+    int bw;   // torch's block width
+    int nit;  // next_pow2(S) / 64: the softmax's elements per lane
+};
+
+// what torch's thread x of bw sums of the row q[0 .. S) stored at d[shift ..] (d 16-byte aligned)
+__device__ __forceinline__ float torch_vec_thread_sum(const float *d, int S, int shift, int x, int bw) {
+    float a0 = 0.0f, a1 = 0.0f, a2 = 0.0f, a3 = 0.0f;
+    int end = S;
+    if (shift > 0) {
+        if (x >= shift && x < 4) a0 = a0 + d[x];
+        end = S + shift - 4;
+        d += 4;
+    }
+    for (int v = x; 4 * v + 3 < end; v += bw) {
+        const float4 t = *reinterpret_cast<const float4 *>(d + 4 * v);
+        a0 = a0 + t.x;
+        a1 = a1 + t.y;
+        a2 = a2 + t.z;
+        a3 = a3 + t.w;
+    }
+    const int tail = end - end % 4 + x;
+    if (tail < end) a0 = a0 + d[tail];
+    return ((a0 + a1) + a2) + a3;
+}
+
+template <int IT>
+__global__ __launch_bounds__(kInvLanes) void k_inverse_rows_wide(InvHead h0, InvHead h1, InvPlan p0, InvPlan p1, int n,
+                                                                  int probs) {
+    __shared__ __attribute__((aligned(16))) float rows[kInvWaves][kInvWideRow];
+    const InvHead h = blockIdx.y ? h1 : h0;
+    const InvPlan plan = blockIdx.y ? p1 : p0;
+    const int l = threadIdx.x & (kWave - 1);
+    float *lds = rows[threadIdx.x >> 6];
+    const int S = h.S, nit = plan.nit, bw = plan.bw;
+    for (long long row = (long long)blockIdx.x * kInvWaves + (threadIdx.x >> 6); row < n;
+         row += (long long)gridDim.x * kInvWaves) {
+        const long long base = row * h.stride;
+        float e[IT];  // logits, exponentials, probabilities, then support * p of elements l + 64 it
+        if (probs) {
+#pragma unroll
+            for (int it = 0; it < IT; ++it) {
+                const int idx = l + kWave * it;
+                e[it] = idx < S ? static_cast<const float *>(h.in)[base + idx] : 0.f;
+            }
+        } else {
+#pragma unroll
+            for (int it = 0; it < IT; ++it) {
+                const int idx = l + kWave * it;
+                e[it] = -INFINITY;
+                if (idx < S) e[it] = h.f16 ? load_elem<true>(h.in, base + idx) : load_elem<false>(h.in, base + idx);
+            }
+            float m = e[0];
+#pragma unroll
+            for (int it = 0; it < IT; ++it)
+                if (it < nit) m = m > e[it] ? m : e[it];
+            for (int o = kWave >> 1; o > 0; o >>= 1) {
+                const float b = __shfl_xor(m, o, kWave);
+                m = m < b ? b : m;
+            }
+            float s = 0.0f;
+#pragma unroll
+            for (int it = 0; it < IT; ++it)
+                if (it < nit) {
+                    e[it] = ::expf(e[it] - m);
+                    s = s + e[it];
+                }
+            for (int o = kWave >> 1; o > 0; o >>= 1) s = s + __shfl_xor(s, o, kWave);
+#pragma unroll
+            for (int it = 0; it < IT; ++it) e[it] = (s == 0.f) ? NAN : e[it] / s;
+        }
+#pragma unroll
+        for (int it = 0; it < IT; ++it) {
+            const int idx = l + kWave * it;
+            e[it] = idx < S ? (float)(h.lo + idx) * e[it] : 0.f;
+        }
+        float acc;
+        if (!plan.vec) {  // 65 <= S < 128: bw = 64, elements l and l + 64 are this lane's own
+            const float v0 = 0.0f + e[0];
+            const float v1 = (l + kWave < S) ? 0.0f + e[1] : 0.0f;
+            acc = ((v0 + v1) + 0.0f) + 0.0f;
+        } else {
+            const int shift = (int)((row * S) & 3);
+#pragma unroll
+            for (int it = 0; it < IT; ++it) {
+                const int idx = l + kWave * it;
+                if (idx < S) lds[shift + idx] = e[it];
+            }
+            // the row is this wave's alone: its LDS writes have landed once the counter drains
+            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+            float t[4] = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                const int x = l + kWave * k;
+                if (x < bw) t[k] = torch_vec_thread_sum(lds, S, shift, x, bw);
+            }
+            if (bw == 256)
+                acc = (t[0] + t[2]) + (t[1] + t[3]);
+            else if (bw == 128)
+                acc = t[0] + t[1];
+            else
+                acc = t[0];
+            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // (read before the next row overwrites it)
+        }
+        const int width = bw < kWave ? bw : kWave;
+        for (int o = 1; o < width; o <<= 1) acc = acc + __shfl_down(acc, o, kWave);
+        if (l == 0) h.out[row] = torch_inv_h(acc);
+    }
+}
+
+// ReduceConfig::set_block_dimension for torch.sum over the last dimension of a contiguous float32
+// [n, S] tensor (MAX_NUM_THREADS 512, input_vec_size 4, wave 64)
+static int last_pow2_int(int64_t v) {
+    int p = 1;
+    while (2 * (int64_t)p <= v) p <<= 1;
+    return p;
+}
+
+static void inverse_sum_plan(int S, int n, int *vectorized, int *block_width) {
+    constexpr int kMaxThreads = 512;
+    int64_t dim0 = S;
+    *vectorized = S >= 128;
+    if (*vectorized) dim0 /= 4;
+    const int d0 = dim0 < kMaxThreads ? last_pow2_int(dim0) : kMaxThreads;
+    const int d1 = n < kMaxThreads ? last_pow2_int(n) : kMaxThreads;
+    int w = d0 < kWave ? d0 : kWave;
+    const int hgt = d1 < kMaxThreads / w ? d1 : kMaxThreads / w;
+    w = d0 < kMaxThreads / hgt ? d0 : kMaxThreads / hgt;
+    *block_width = w;
+}
+
 // the table of mz_set_half_exp_table per device (allocated once, never freed: captured graphs keep
 // its address)
 constexpr int kMaxDevices = 64;
@@ -860,10 +1022,11 @@ int mz_joint_action_wide(mz_batch *b, const void *pred_logits, int dtype, int nu
                         factor_cols, actions, joint_out);
 }
 
-int mz_inverse_transform(mz_batch *b, void *stream, int stage, int n, const void *value_in, int value_dtype,
-                         int64_t value_stride, int value_lo, int value_hi, const void *reward_in, int reward_dtype,
-                         int64_t reward_stride, int reward_lo, int reward_hi, float *value_out, float *reward_out) {
-    const char *fn = "mz_inverse_transform";
+// mz_inverse_transform (wide false: supports past one wave are refused) and mz_inverse_transform_wide
+static int inverse_transform(const char *fn, bool wide, mz_batch *b, void *stream, int stage, int n,
+                             const void *value_in, int value_dtype, int64_t value_stride, int value_lo, int value_hi,
+                             const void *reward_in, int reward_dtype, int64_t reward_stride, int reward_lo,
+                             int reward_hi, float *value_out, float *reward_out) {
     hipStream_t s = (hipStream_t)stream;
     if (b) {  // the handle's device current, its stream
         int B = 0, A = 0;
@@ -873,8 +1036,9 @@ int mz_inverse_transform(mz_batch *b, void *stream, int stage, int n, const void
     if (stage != MZ_INV_LOGITS && stage != MZ_INV_PROBS && stage != MZ_INV_EXPECTATION)
         return glue_fail(MZ_ERR_ARG, fn, "bad stage");
     if (n < 0) return glue_fail(MZ_ERR_ARG, fn, "n must be >= 0");
-    InvHead heads[2] = {};
-    int nh = 0;
+    InvHead heads[2] = {}, wheads[2] = {};  // heads of up to 64 support elements (or scalars); longer ones
+    InvPlan wplans[2] = {};
+    int nh = 0, nw = 0, wide_it = 0;
     const struct {
         const void *in;
         int dtype;
@@ -891,20 +1055,50 @@ int mz_inverse_transform(mz_batch *b, void *stream, int stage, int n, const void
         if (a.hi < a.lo) return glue_fail(MZ_ERR_ARG, fn, "support hi < lo");
         const int64_t S = (int64_t)a.hi - a.lo + 1;
         if (stage != MZ_INV_EXPECTATION) {
-            if (S > kWave) return glue_fail(MZ_ERR_UNSUPPORTED, fn, "support size > 64 (one lane per support element)");
+            if (S > kWave && !wide)
+                return glue_fail(MZ_ERR_UNSUPPORTED, fn, "support size > 64 (one lane per support element)");
+            if (S > kInvWideMax)
+                return glue_fail(MZ_ERR_UNSUPPORTED, fn, "support size > 1024 (torch's softmax changes kernel there)");
             if (a.stride < S) return glue_fail(MZ_ERR_ARG, fn, "row stride below the support size");
+            if (S > kWave) {  // k_inverse_rows_wide, with the plan of torch's sum for this S and n
+                InvPlan plan{};
+                inverse_sum_plan((int)S, n > 0 ? n : 1, &plan.vec, &plan.bw);
+                plan.nit = 2;
+                while (plan.nit * kWave < S) plan.nit <<= 1;
+                if (plan.nit > wide_it) wide_it = plan.nit;
+                wplans[nw] = plan;
+                wheads[nw++] = InvHead{a.in, a.out, (long long)a.stride, a.lo, (int)S, a.dtype == MZ_DT_F16};
+                continue;
+            }
         } else if (a.stride < 1) {
             return glue_fail(MZ_ERR_ARG, fn, "row stride must be >= 1");
         }
         heads[nh++] = InvHead{a.in, a.out, (long long)a.stride, a.lo, (int)(S > kWave ? 0 : S), a.dtype == MZ_DT_F16};
     }
-    if (nh == 0) return glue_fail(MZ_ERR_ARG, fn, "both heads are null");
+    if (nh + nw == 0) return glue_fail(MZ_ERR_ARG, fn, "both heads are null");
     if (n == 0) return MZ_OK;
-    if (stage == MZ_INV_EXPECTATION) {
+    if (nw) {
+        const long long blocks = ((long long)n + kInvWaves - 1) / kInvWaves;
+        const dim3 grid((unsigned)(blocks < kInvMaxGrid ? blocks : kInvMaxGrid), nw);
+        const int probs = stage == MZ_INV_PROBS ? 1 : 0;
+#define MZ_INV_WIDE_LAUNCH(IT)                                                                              \
+    hipLaunchKernelGGL(k_inverse_rows_wide<IT>, grid, dim3(kInvLanes), 0, s, wheads[0], wheads[1], wplans[0], \
+                       wplans[1], n, probs)
+        if (wide_it == 2)
+            MZ_INV_WIDE_LAUNCH(2);
+        else if (wide_it == 4)
+            MZ_INV_WIDE_LAUNCH(4);
+        else if (wide_it == 8)
+            MZ_INV_WIDE_LAUNCH(8);
+        else
+            MZ_INV_WIDE_LAUNCH(16);
+#undef MZ_INV_WIDE_LAUNCH
+    }
+    if (nh && stage == MZ_INV_EXPECTATION) {
         const long long blocks = ((long long)n + kInvLanes - 1) / kInvLanes;
         hipLaunchKernelGGL(k_inverse_scalars, dim3((unsigned)(blocks < kInvMaxGrid ? blocks : kInvMaxGrid), nh),
                            dim3(kInvLanes), 0, s, heads[0], heads[1], n);
-    } else {
+    } else if (nh) {  // (0: every head went to the wide kernel)
         const long long blocks = ((long long)n + kInvWaves - 1) / kInvWaves;
         hipLaunchKernelGGL(k_inverse_rows, dim3((unsigned)(blocks < kInvMaxGrid ? blocks : kInvMaxGrid), nh),
                            dim3(kInvLanes), 0, s, heads[0], heads[1], n, stage == MZ_INV_PROBS ? 1 : 0);
@@ -912,6 +1106,31 @@ int mz_inverse_transform(mz_batch *b, void *stream, int stage, int n, const void
     if (b) mz_internal_enqueued(b);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return mz_internal_fail(MZ_ERR_DEVICE, hipGetErrorString(e));
+    return MZ_OK;
+}
+
+int mz_inverse_transform(mz_batch *b, void *stream, int stage, int n, const void *value_in, int value_dtype,
+                         int64_t value_stride, int value_lo, int value_hi, const void *reward_in, int reward_dtype,
+                         int64_t reward_stride, int reward_lo, int reward_hi, float *value_out, float *reward_out) {
+    return inverse_transform("mz_inverse_transform", false, b, stream, stage, n, value_in, value_dtype, value_stride,
+                             value_lo, value_hi, reward_in, reward_dtype, reward_stride, reward_lo, reward_hi, value_out,
+                             reward_out);
+}
+
+int mz_inverse_transform_wide(mz_batch *b, void *stream, int stage, int n, const void *value_in, int value_dtype,
+                              int64_t value_stride, int value_lo, int value_hi, const void *reward_in,
+                              int reward_dtype, int64_t reward_stride, int reward_lo, int reward_hi, float *value_out,
+                              float *reward_out) {
+    return inverse_transform("mz_inverse_transform_wide", true, b, stream, stage, n, value_in, value_dtype,
+                             value_stride, value_lo, value_hi, reward_in, reward_dtype, reward_stride, reward_lo,
+                             reward_hi, value_out, reward_out);
+}
+
+int mz_inverse_sum_plan(int S, int n, int *vectorized, int *block_width) {
+    if (!vectorized || !block_width) return mz_internal_fail(MZ_ERR_ARG, "mz_inverse_sum_plan: null argument");
+    if (S < 1 || n < 1) return mz_internal_fail(MZ_ERR_ARG, "mz_inverse_sum_plan: S and n must be >= 1");
+    if (S > kInvWideMax) return mz_internal_fail(MZ_ERR_UNSUPPORTED, "mz_inverse_sum_plan: S > 1024");
+    inverse_sum_plan(S, n, vectorized, block_width);
     return MZ_OK;
 }
 

@@ -16,7 +16,8 @@ and the per-simulation glue stay on the device:
 (with `wide_actions`: mz_root_glue_wide, mz_joint_action_wide, mz_policy_glue_wide, for action spaces
 of 65..255; with `fused_transforms`: the inverse transforms of the value and reward heads are one
 mz_inverse_transform launch, torch's arithmetic on this device restated bit for bit, instead of the
-model's ~46 torch kernels)
+model's ~46 torch kernels; with `wide_supports` as well, mz_inverse_transform_wide does the same for
+supports of 65..1024 elements)
 
 so a search has no host synchronisation between `prepare` and the final readback.  The root
 preprocessing (mcts_sampled.py:51-106) is split: the host draws from `np_random` (the Dirichlet
@@ -117,8 +118,12 @@ class _SearchLoop:
     Every input is copied into the static buffers before a run, and the tree seed lives in device
     memory (mz_reseed), so replaying the graph is a new search."""
 
-    def __init__(self, tb, B, A, N, cur, hidden, dev, model, root_mode=None, wide=False, fused=None):
+    def __init__(self, tb, B, A, N, cur, hidden, dev, model, root_mode=None, wide=False, fused=None,
+                 wide_supports=False):
         self.tb, self.B, self.A, self.N, self.cur, self.dev = tb, B, A, N, cur, dev
+        # supports of 65 .. 1024 elements take LOGITS through mz_inverse_transform_wide (SampledMCTS's
+        # wide_supports) instead of EXPECTATION behind torch's softmax, multiply and sum
+        self.wide_supports = bool(wide_supports)
         # fused = (value (lo, hi), reward (lo, hi)) or the string "identity": the inverse transforms of
         # the two heads run as one mz_inverse_transform launch into inv_v / inv_r, which the tree call
         # reads (SampledMCTS's fused_transforms); None: the model's own transforms
@@ -316,9 +321,13 @@ class _SearchLoop:
                 raise ValueError(f"fused_transforms: head logits of shape {tuple(t.shape)} for the support "
                                  f"[{lo}, {hi}] of the config and {B} roots")
             heads.append(t)
-        stage = FUSED_STAGE
-        if any(hi - lo + 1 > MAX_FUSED_SUPPORT for lo, hi in self.fused):
-            stage = MZ_INV_EXPECTATION  # (a support past one wave, the reference's default [-300, 300])
+        stage, call = FUSED_STAGE, lib.mz_inverse_transform
+        longest = max(hi - lo + 1 for lo, hi in self.fused)
+        if longest > MAX_FUSED_SUPPORT:  # a support past one wave, the reference's default [-300, 300]
+            if self.wide_supports and longest <= MAX_WIDE_SUPPORT:
+                call = lib.mz_inverse_transform_wide
+            else:
+                stage = MZ_INV_EXPECTATION
         if stage == MZ_INV_LOGITS:
             heads = [t if t.stride(1) == 1 else t.contiguous() for t in heads]
         elif stage == MZ_INV_PROBS:
@@ -327,10 +336,10 @@ class _SearchLoop:
             heads = [torch.sum(sup * torch.softmax(t, dim=-1), dim=-1, keepdim=True)
                      for t, sup in zip(heads, self.inv_support)]
         (v, r), ((vlo, vhi), (rlo, rhi)) = heads, self.fused
-        check(lib, lib.mz_inverse_transform(h, None, stage, B,
-                                            C.c_void_p(v.data_ptr()), _dtype_code(v), v.stride(0), vlo, vhi,
-                                            C.c_void_p(r.data_ptr()), _dtype_code(r), r.stride(0), rlo, rhi,
-                                            C.c_void_p(self.inv_v.data_ptr()), C.c_void_p(self.inv_r.data_ptr())),
+        check(lib, call(h, None, stage, B,
+                        C.c_void_p(v.data_ptr()), _dtype_code(v), v.stride(0), vlo, vhi,
+                        C.c_void_p(r.data_ptr()), _dtype_code(r), r.stride(0), rlo, rhi,
+                        C.c_void_p(self.inv_v.data_ptr()), C.c_void_p(self.inv_r.data_ptr())),
               "inverse_transform")
         return True
 
@@ -454,6 +463,7 @@ MAX_FUSED_SUPPORT = 64  # mz_inverse_transform's LOGITS / PROBS stages: one lane
 # how much of softmax -> _inv_phi -> _inv_h the fused launch computes for supports of up to 64
 # elements; longer supports take MZ_INV_EXPECTATION behind torch's softmax and sum
 FUSED_STAGE = MZ_INV_LOGITS
+MAX_WIDE_SUPPORT = 1024  # mz_inverse_transform_wide's LOGITS / PROBS stages (torch's softmax_warp_forward)
 
 
 def _support_bounds(support) -> Tuple[int, int]:
@@ -472,7 +482,7 @@ class SampledMCTS:
 
     def __init__(self, config, np_random: np.random.RandomState = None, *, lib=None, use_graph: bool = True,
                  root_shard: Tuple[int, int, int] = None, device_root: bool = True, wide_actions: bool = None,
-                 fused_transforms: bool = None):
+                 fused_transforms: bool = None, wide_supports: bool = None):
         """`fused_transforms`: compute the inverse value / reward transforms of every simulation
         (core/config.py:487-499) with one mz_inverse_transform launch instead of the model's
         `inverse_value_transform` / `inverse_reward_transform`; the search calls `model.dynamics` and
@@ -482,6 +492,13 @@ class SampledMCTS:
         none).  The results are those of the torch chain on the same device, bit for bit.  A model with
         `recurrent_inference_device`, or head logits that are not float32 / autocast float16, keep the
         model's own transforms.
+
+        `wide_supports`: with `fused_transforms`, supports of 65 to 1,024 elements (the reference's
+        default DiscreteSupport(-300, 300)) also get the whole chain in that one launch, through
+        mz_inverse_transform_wide; without it they keep torch's softmax, multiply and sum and only
+        _inv_h is fused.  None reads `config.wide_supports` (False when the config has none).  Longer
+        supports keep that route either way, and the flag alone, without `fused_transforms`, has no
+        effect.
 
         `wide_actions`: run the driver glue through the _wide entry points (include/mzdriver.h), which
         take action spaces up to 255 instead of 64.  None reads `config.wide_actions` (False when the
@@ -519,6 +536,9 @@ class SampledMCTS:
             else:
                 self.fused_transforms = (_support_bounds(config.value_support),
                                          _support_bounds(config.reward_support))
+        if wide_supports is None:
+            wide_supports = getattr(config, "wide_supports", False)
+        self.wide_supports = bool(wide_supports)
         self.np_random = np.random if np_random is None else np_random
         self._lib = lib
         if root_shard is not None:
@@ -686,7 +706,8 @@ class SampledMCTS:
             tb = self._tree(B, seed, dev)
             # the discount is a kernel argument of the recorded launches
             key = (threading.get_ident(), id(tb), id(model), N, cur, float(eps), float(sampled_tau), float(disc),
-                   tuple(hidden.shape), hidden.dtype, root_mode, self.wide_actions, self.fused_transforms)
+                   tuple(hidden.shape), hidden.dtype, root_mode, self.wide_actions, self.fused_transforms,
+                   self.wide_supports)
             with _LOCK:
                 for k in [k for k, v in _LOOPS.items() if v.model_ref() is None]:
                     del _LOOPS[k]  # loops (graph, pool) of models that no longer exist
@@ -696,7 +717,8 @@ class SampledMCTS:
                 # addresses it was recorded with (re-homed weights, weights.FlatWeights, need a new one)
                 if st is None or st.model_ref() is not model or st.storage != sig or st.tb is not tb:
                     st = _LOOPS[key] = _SearchLoop(tb, B, A, N, cur, hidden, dev, model, root_mode,
-                                                   wide=self.wide_actions, fused=self.fused_transforms)
+                                                   wide=self.wide_actions, fused=self.fused_transforms,
+                                                   wide_supports=self.wide_supports)
                     st.storage = sig
                 _LOOPS.move_to_end(key)
                 while len(_LOOPS) > max(_MAX_LOOPS, 1):  # least recently used first
