@@ -817,6 +817,71 @@ __device__ __forceinline__ double cdf_terms(int A, const float *sw, double *sp, 
     if (l == A - 1) cp = 1.0;
     return cp;
 }
+// std::discrete_distribution's cumulative table (libstdc++ random.tcc:2656-2690, as cdf_lane) for
+// A <= 16 in registers.  Each lane holds its own weight wl (0 for lanes >= A); lane j's operand
+// reaches every lane of its DPP row (16 lanes) through row_newbcast:j, inside a VALU instruction
+// and with no wait, so the sequential double sum and the sequential prefix sums run without
+// v_readlane and without LDS.  N terms (A <= N): trailing +0.0 terms are exact no-ops on the
+// non-negative sums, so N only has to cover A -- the class (4, 8, 12, 16) is picked once per call,
+// not per term.  Lane a returns cp[a] (cp[A-1] forced to 1.0).  Same operand values, operations and
+// order as cdf_lane and cdf_long, term for term: bit-identical.  Lanes >= 16 see their own rows'
+// zeros and return finite values nobody reads (masked by l < A at every use).
+// Precondition: row_newbcast reads the source lane's register only if that lane is active, so
+// lanes 0..15 of the wave must be active, in wave-uniform control flow.  Holds at both call sites,
+// k_chain3's draw wave and wave 0's own draw when the hand-over runs out of polls: whole waves in
+// straight-line code behind uniform branches (the wave index, A, the slot's readfirstlane).
+// Every other expansion keeps the LDS form (cdf_terms) or v_readlane (cdf_lane): routed through
+// this table, wave 0 of the three-wave k_chain3 and k_tree measured slower (they hide other work
+// behind the LDS waits; profiles/cdf_row/).
+// The broadcasts are convergent and stay outside the (l < A) select below: the compiler runs the
+// sum's conversions and adds and the division under an exec mask of l < A, behind the N
+// v_mov_b32_dpp, which all run with the full mask; a broadcast moved into that block would find
+// its source lanes >= A switched off.  (Typed builtin with bound_ctrl: the double moves with one
+// v_mov_b64_dpp per term; the float's move does not fold into its conversion, which sits in the
+// masked block.)
+template <int J, class T>
+__device__ __forceinline__ T row_bcast(T x) {
+    return __builtin_amdgcn_update_dpp((T)0, x, 0x150 + J, 0xf, 0xf, true);  // row_newbcast:J
+}
+template <int J, int N, class T>
+struct RowBcast {  // o[j] = lane j's x for j in [J, N) (the DPP control is an immediate)
+    static __device__ __forceinline__ void run(T x, T *o) {
+        o[J] = row_bcast<J, T>(x);
+        RowBcast<J + 1, N, T>::run(x, o);
+    }
+};
+template <int N, class T>
+struct RowBcast<N, N, T> {
+    static __device__ __forceinline__ void run(T, T *) {}
+};
+template <int N>
+__device__ __forceinline__ double cdf_row(int A, float wl) {
+    static_assert(N <= 16, "one DPP row");
+    const int l = lane_id();
+    float w[N];
+    RowBcast<0, N, float>::run(wl, w);
+    double sum = 0.0;
+#pragma unroll
+    for (int j = 0; j < N; ++j) sum += (double)w[j];
+    const double p = (l < A) ? (double)wl / sum : 0.0;
+    double pj[N];
+    RowBcast<0, N, double>::run(p, pj);
+    double acc = pj[0], cp = (l == 0) ? pj[0] : 0.0;
+#pragma unroll
+    for (int j = 1; j < N; ++j) {
+        acc = acc + pj[j];
+        cp = sel_lane(cp, acc, 1ull << j);
+    }
+    if (l == A - 1) cp = 1.0;
+    return cp;
+}
+// the class (4, 8, 12, 16 terms) picked once per call; 2 <= A <= 16, wl = 0 on lanes >= A
+__device__ __forceinline__ double cdf_short(int A, float wl) {
+    if (A <= 4) return cdf_row<4>(A, wl);
+    if (A <= 8) return cdf_row<8>(A, wl);
+    if (A <= 12) return cdf_row<12>(A, wl);
+    return cdf_row<16>(A, wl);
+}
 // A > 16: batches of 16 terms, then the rest in steps of 4 up to A rounded up to 4 (27m: 36 terms,
 // not three batches of 16); each batch's LDS reads issued together ahead of its adds
 template <class F2 = NoWork>
@@ -3425,8 +3490,8 @@ int chain3_lds_bytes(int nc) { return Chain3Layout<0>(nc).total; }
 // cleared between workgroups, so wave 0 clears the slot and one s_barrier, taken by all four waves
 // behind their round-1 load issue and before any early return, separates the clear from the publish.
 // Wave 0 polls the slot a bounded number of times (kDrawPolls); if the bound runs out it draws itself
-// with cdf_lane (no LDS: the draw wave may still be using sW / sP), bit-identical, so a launch can
-// never hang on the hand-over.
+// in registers (cdf_row, cdf_lane past 16 actions; no LDS: the draw wave may still be using sW / sP),
+// bit-identical, so a launch can never hang on the hand-over.
 constexpr int kDrawSlot = 4;  // dword of the oX region (0, 1: min / max; stamps from dword 16)
 #ifndef MZ_CHAIN3_POLLS
 #define MZ_CHAIN3_POLLS 128  // ~100 cycles each: several times the draw wave's ~2,000 cycles
@@ -3501,7 +3566,9 @@ __global__ __launch_bounds__(W4 ? 256 : 192) void k_chain3(char *base, const flo
             asm volatile("s_waitcnt lgkmcnt(0)" : "+s"(nx) : : "memory");
             int a = 0;
             if (A >= 2) {
-                const double cp = cdf_bcast(bet, A, (float *)(smem + L.oW), (double *)(smem + L.oP));
+                // (up to 16 actions in registers, cdf_row: this wave has nothing to hide behind LDS waits)
+                const double cp = (A <= 16) ? cdf_short(A, (l < A) ? bet : 0.f)
+                                            : cdf_bcast(bet, A, (float *)(smem + L.oW), (double *)(smem + L.oP));
                 const double u = draw_u((unsigned)nx[0], (unsigned)nx[1]);
                 a = __popcll(ballot(l < A && cp < u));  // lower_bound
             }
@@ -3923,7 +3990,8 @@ __global__ __launch_bounds__(W4 ? 256 : 192) void k_chain3(char *base, const flo
             // wave's), from the same words in the same order
             fell = 1;
             if (A >= 2) {
-                const double cp = cdf_lane((l < A) ? (double)bet : 0.0, A);
+                const float w = (l < A) ? bet : 0.f;
+                const double cp = (A <= 16) ? cdf_short(A, w) : cdf_lane((double)w, A);
                 const double u = draw_u(h.nxt[0], h.nxt[1]);
                 a = __popcll(ballot(l < A && cp < u));  // lower_bound
             }
