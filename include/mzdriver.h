@@ -205,6 +205,11 @@ int mz_fused_kernel(mz_batch *b, char *out, int len);
  * k_chain3.  The name above is the same for both. */
 int mz_fused_waves(mz_batch *b, int *waves);
 
+/* The kernel this handle launches for mz_prepare and mz_prepare_select, as a NUL-terminated name
+ * written into out[len]: "k_prepare1" (agent_num = 1, sampled_times = 1, action_space_size <= 64:
+ * the role-specialised kernel, unless MZ_PREPARE_GENERAL is set at mz_create) or "k_prepare". */
+int mz_prepare_kernel(mz_batch *b, char *out, int len);
+
 /* Release what the library keeps for reuse across handles: device arenas of destroyed handles
  * (at most 2 GiB / 16 blocks per process, reused by a handle of the same size, as the reference's
  * per-search Tree_batch re-creates them, mcts_sampled.py:89), pinned host stages (at most

@@ -1415,6 +1415,9 @@ __global__ __launch_bounds__(256) void k_prepare(const Params *__restrict__ prm,
     __shared__ unsigned w0[kMtN];
     const int t = blockIdx.x;
     const int tid = threadIdx.x;
+    // (MZ_SPANS builds: slot 0 of the launch spans -- start, the seeding barrier, the last twist
+    // round and the end, all on wave 0, which takes every barrier of the workgroup)
+    const unsigned long long rt0 = span_open();
     // the handle's error word starts clean (no runtime memset node in captured graphs).  A tree's
     // error also stays in its header, and every later kernel re-reports the errors of dead trees,
     // so an error raised by another block before this store is not lost.
@@ -1461,6 +1464,7 @@ __global__ __launch_bounds__(256) void k_prepare(const Params *__restrict__ prm,
     // (the twist exchanges LDS data only: barriers that leave the tempered words' global stores in
     // flight instead of draining them at every phase)
     lds_barrier();
+    if (tid < kWave) span_end(0, 1);
     int nb = g.W / kMtN;
     // One twist per 624-word block (std::mt19937::_M_gen_rand), one barrier each: thread k < 227
     // computes the three words k, k + 227, k + 454 of the new state in registers.  Word k uses old
@@ -1502,6 +1506,7 @@ __global__ __launch_bounds__(256) void k_prepare(const Params *__restrict__ prm,
     // a full workgroup barrier (stores drained) first
     if (g.A > kMaxActions || 2 * a.K * g.N > kRngWin) __syncthreads();
     if (tid >= kWave) return;
+    span_end(0, 2);
 
     // ---- root expansion by wave 0 ----
     const int l = tid;
@@ -1605,6 +1610,7 @@ __global__ __launch_bounds__(256) void k_prepare(const Params *__restrict__ prm,
         }
         if (err) atomicOr(d.err(), err);
     }
+    span_close(0, rt0);
 }
 
 // Bootstrap recurrence b = r + disc * b (cnode.cpp:448) over `n` levels, lane-parallel: level
@@ -6158,6 +6164,256 @@ __global__ __launch_bounds__(kTreeWavesN<NC> * 64) void k_tree(char *base, const
                        ((unsigned long long)(Dn & 0xffff) << 32) | ((unsigned long long)moved << 48), rt0, rm1, rm2, rm3);
 }
 
+// --------------------------------------------------------------------------------------------
+// k_prepare1: k_prepare for handles with agent_num = 1, sampled_times = 1 and A <= 64 (mz_create
+// picks it; MZ_PREPARE_GENERAL=1 keeps k_prepare).  The same engine stream, records, header, path,
+// statistics and selection outputs, byte for byte, from five waves -- the root wave and four twist
+// waves, the first of which also seeds -- instead of one serial chain on every wave:
+//   wave 0 (the root wave) issues the root's input loads at entry and takes the seeding barrier
+//     with them in flight.  Behind it its lanes compute engine words 0 .. 33 of block 0 from the
+//     seeded state into registers (the twist's own expressions: word k < 227 reads old words only),
+//     then it builds the distribution, stores everything the drawn action does not feed (the
+//     root's records, the child's C / PP / Par / Q, path, idx_x, idy, the statistics), draws, and
+//     stores the child's A / Bn / D, act and the header (nxt[j] by the lane that holds word
+//     cursor + j).  No wait for memory stands between the draw and these stores.
+//   wave 1 loads the seed word and the checkpoint row and replays the 39 pieces into LDS (or runs
+//     the sequential chain: no table, or a seed value beyond it), then twists with waves 2 .. 4.
+//   waves 1 .. 4: the twist, 227 lanes, as k_prepare, the tempered words' stores left in flight.
+// Barriers: s_barrier counts every wave of the workgroup that has not ended, so the root wave takes
+// each of the twist's nb - 1 barriers too, at the points of its own work where the twist waves are
+// about to arrive (spans, profiles/prepare_chain/): up to 16 actions the second right behind its
+// engine words and the third behind the distribution; past 16 actions, where the distribution is
+// two rounds long, between its two sums and behind it; the rest at its end, where it has nothing
+// left to do.  Ending instead, or taking the seeding barrier behind its own round trip, held the
+// twist -- the launch's longest arm -- back by 0.4 us.  A mismatch could not hang the launch: the
+// barrier completes among the waves that are left.
+// The first 14 argument dwords arrive preloaded in SGPRs; every array offset follows from them
+// (arena_hot) or from the argument line `io`: no wave reads the Params block.
+// --------------------------------------------------------------------------------------------
+struct Prep1IO {
+    int *idx_x, *idy, *act;  // non-null: also the first selection (mz_prepare_select)
+    const unsigned *cp;      // the seeding checkpoints (null: the chain) and their rows
+    unsigned cp_n;
+    int W, root_offset;
+    float eps;
+    float one_minus_rho;
+    unsigned o_R, o_D;
+    int nb;  // W / kMtN
+};
+static_assert(sizeof(Prep1IO) == 64, "k_prepare1: one 64-byte argument line");
+constexpr int kPrep1Waves = 5;
+constexpr int kPrep1Words = kNxt + 2;  // engine words the root wave computes itself: the draw's two, then nxt
+static_assert(kPrep1Words <= kWave && kPrep1Words + 397 <= kMtN && kPrep1Words <= 227, "root wave's engine words");
+__global__ __launch_bounds__(kPrep1Waves *kWave) void k_prepare1(char *base, const float *reward, const float *value,
+                                                                 const float *policy, const float *beta,
+                                                                 const float *noise, int bak, int pps, Prep1IO io) {
+    __shared__ unsigned mt[kMtN];
+    __shared__ unsigned mt2[kMtN];
+    // the root wave's scratch for cdf_bcast (A > 16).  cdf_long issues its last three reads together,
+    // past A but never past index 63 (a0 <= 48, twelve entries): the eight entries of slack are unused
+    __shared__ __attribute__((aligned(16))) double cdf_p[kWave + 8];
+    __shared__ __attribute__((aligned(16))) float cdf_w[kWave + 8];
+    const int t = blockIdx.x;
+    const int l = threadIdx.x & (kWave - 1);
+    const int wv = uni((int)(threadIdx.x >> 6));
+    const unsigned B = (unsigned)bak & 0xffffffu, P = (unsigned)pps & 0xffffu, PS = (unsigned)pps >> 16;
+    const int A = (bak >> 24) & 0x7f;
+    Dev d;
+    d.base = (gchar *)base;
+    arena_hot(d, B, P, PS);
+    d.o_R = io.o_R;
+    d.o_D = io.o_D;
+
+    if (wv == 0) {
+        // ======== the root wave ========
+        const unsigned long long rt0 = span_open();
+        if (t == 0 && l == 0) *d.err() = 0;  // (as k_prepare)
+        const size_t ib = (size_t)t * A;
+        float pol = (l < A) ? policy[ib + l] : 0.f;
+        float bet = (l < A) ? beta[ib + l] : 0.f;
+        float noi = (l < A) ? noise[ib + l] : 0.f;
+        float r = reward[t];
+        float v = value[t];
+        float lp0 = d.lp()[0];
+        long long *st = d.stats() + (size_t)t * MZ_S_COUNT;
+        static_assert(MZ_S_SELECTS == 0 && MZ_S_PATH_EDGES == 1 && MZ_S_EXPANDS == 3 && MZ_S_NEW_CHILDREN == 4,
+                      "k_prepare1: the counters it advances, one per lane");
+        long long st_old = (l <= MZ_S_NEW_CHILDREN) ? st[l] : 0;
+        const int nb = io.nb;
+        // the seeding barrier with the loads above in flight (the barrier's asm keeps them ahead of
+        // it): the twist must not wait for this wave's round trip
+        lds_barrier();
+        int taken = 1;  // barriers this wave has taken, of the nb every other wave takes
+        auto bar = [&]() {
+            if (taken < nb) lds_barrier();
+            ++taken;
+        };
+        // engine words 0 .. 33 of block 0, lane l word l (lanes past them compute words nobody reads),
+        // into registers before this wave takes the barrier behind which the twist overwrites `mt`
+        unsigned z = mt_temper(mt[l + 397] ^ mt_twist(mt[l], mt[l + 1]));
+        if (A <= 16) {
+            // the twist's second barrier right away, the loads still in flight: the twist waves get
+            // there one round from now, about when the loads land
+            asm volatile("" : "+v"(z));
+            bar();
+        }
+        // (one round trip: every load above was issued before the first wait, none sunk to its use)
+        asm volatile("" : "+v"(pol), "+v"(bet), "+v"(noi), "+v"(r), "+v"(v), "+v"(lp0), "+v"(st_old), "+v"(z));
+        const bool sel = io.idx_x != nullptr;
+        const float eps = io.eps;
+        const int err = (value_lim(1, io.one_minus_rho) != 1) ? kErrValueSet : 0;
+        const int D = (sel && !err) ? 1 : 0;  // nc = 1: the forced round-robin takes child 0 (cnode.cpp:398-399)
+        // the distribution: in registers up to 16 actions (about one twist round long: the next
+        // barrier behind it), else LDS broadcasts (about two: a barrier between its sums, one behind)
+        double cp = 0.0;
+        if (A >= 2) {
+            if (A <= 16) {
+                cp = cdf_short(A, (l < A) ? bet : 0.f);
+            } else {
+                cp = cdf_bcast(bet, A, cdf_w, cdf_p, NoWork(), bar);
+            }
+            bar();
+        }
+        // every lane's prior as if its action were drawn (one draw: betahat_prob = 1 / 1)
+        const float bh = 1.0f;
+        float prior = (eps > 0) ? (pol * (1 - eps) + noi * eps) : pol;
+        prior = prior * bh / bet;
+        const size_t gi = (size_t)t * P;
+        if (l == 0) {
+            // root: CNode(1,1,1,1,true) (cnode.cpp:217), expanded, visit += 1, subtree.update(value, 0)
+            float ws = 0.f, tw = 0.f;
+            tw += lp0;
+            ws += lp0 * v;
+            const float val = ws / tw;  // (nc = 1)
+            d.A()[gi] = make_int4(1, f2i(1.0f), f2i(val), f2i(r));
+            d.Bn()[gi] = make_int4(1, pack_y(1, 0, 0), f2i(v), 0);
+            d.C()[gi] = make_float4(ws, tw, 0.f, 0.f);
+            d.D()[gi] = make_float4(1.f, 1.f, 1.f, 0.f);
+            d.Q()[gi] = 0.f;
+            d.PP()[gi] = 0.f;
+            d.V()[gi * (PS - 1)] = make_int2(0, f2i(v));
+            // the child (node 1), but for what the action feeds
+            d.C()[gi + 1] = make_float4(0.f, 0.f, 0.f, 0.f);
+            d.Q()[gi + 1] = 0.f;
+            d.PP()[gi + 1] = v;
+            d.Par()[gi + 1] = 0;
+            d.path()[(size_t)t * PS] = make_int2(0, 1);
+            if (D == 1) d.path()[(size_t)t * PS + 1] = make_int2(1, 0);
+            if (sel) {
+                io.idx_x[t] = 0;  // the root's hidden_state_index_x
+                io.idy[t] = t;
+            }
+        }
+        {
+            const long long inc = (l >= MZ_S_EXPANDS) ? 1 : ((l <= MZ_S_PATH_EDGES && D == 1) ? 1 : 0);
+            if (l <= MZ_S_NEW_CHILDREN && inc) st[l] = st_old + inc;
+        }
+        int a = 0, cursor = 0;
+        if (A >= 2) {
+            const double u = draw_u((unsigned)rl((int)z, 0), (unsigned)rl((int)z, 1));
+            a = __popcll(ballot(l < A && cp < u));  // lower_bound
+            cursor = 2;
+        }
+        const bool mine = l == a;
+        const int wild = (ballot(mine && !tame_prior(prior)) != 0ull) ? 1 : 0;
+        if (mine) {
+            d.A()[gi + 1] = make_int4(0, f2i(prior), f2i(0.0f), f2i(0.0f));
+            d.Bn()[gi + 1] = make_int4(0, pack_y(0, l, -1), f2i(0.0f), -1);
+            d.D()[gi + 1] = make_float4(pol, bet, bh, 0.f);
+            if (sel) io.act[t] = err ? 0 : l;
+        }
+        int *hw = (int *)(d.hdr() + t);
+        if (l == kWave - 1) {  // cursor .. hot_tag
+            const int tame = (!wild && tame_val(v) && tame_val(r)) ? 1 : 0;
+            const int leaf_y = (D == 1) ? pack_y(0, a, -1) : pack_y(1, 0, 0);
+            int4 *h4 = (int4 *)hw;
+            h4[0] = make_int4(cursor, 2, D, err);
+            h4[1] = make_int4(f2i(0.f), f2i(0.f), 0, D);  // mm_min, mm_max, mm_cnt, leaf
+            h4[2] = make_int4(tame, 1, leaf_y, err ? 0 : 2);  // tame, root_vis, leaf_y, hot_tag (= tot)
+        }
+        if (l >= cursor && l < cursor + kNxt) hw[offsetof(TreeHdr, nxt) / 4 + l - cursor] = (int)z;
+        if (err && l == 0) atomicOr(d.err(), err);
+        span_close(0, rt0);
+        // the twist's remaining barriers, with nothing left to do: a wave that has not ended counts
+        // in every s_barrier of its workgroup, and a wave that waits here delays nobody
+        while (taken < nb) bar();
+        return;
+    }
+
+    // ======== waves 1 .. 4: the seeding (wave 1) and the twist ========
+    const int k = (int)threadIdx.x - kWave;
+    if (wv == 1) {
+        const unsigned seed_v = d.seed()[0] * 2333u + (unsigned)(io.root_offset + t);
+        const unsigned *cp = io.cp;
+        if (cp && seed_v < io.cp_n) {
+            // the seeding chain from the checkpoints: lane j replays words 16j .. 16j + 15
+            if (l < kMtN / kSeedStep) {
+                const int i0 = kSeedStep * l;
+                unsigned x = cp[(size_t)seed_v * kSeedRow + l];
+                mt[i0] = x;
+#pragma unroll
+                for (int i = 1; i < kSeedStep; ++i) {
+                    x = 1812433253u * (x ^ (x >> 30)) + (unsigned)(i0 + i);
+                    mt[i0 + i] = x;
+                }
+            }
+        } else {
+            // std::mt19937::seed on the scalar unit (as k_prepare)
+            unsigned x = (unsigned)__builtin_amdgcn_readfirstlane((int)seed_v);
+            unsigned tt;
+            int v0 = (int)x, v1 = 0, v2 = 0, v3 = 0, v4 = 0, v5 = 0, v6 = 0, v7 = 0, v8 = 0, v9 = 0;
+            asm volatile(MZ_MT_SEED_ASM
+                         : [x] "+s"(x), [t] "=&s"(tt), [v0] "+v"(v0), [v1] "+v"(v1), [v2] "+v"(v2), [v3] "+v"(v3),
+                           [v4] "+v"(v4), [v5] "+v"(v5), [v6] "+v"(v6), [v7] "+v"(v7), [v8] "+v"(v8), [v9] "+v"(v9)
+                         :
+                         : "scc");
+            mt[l] = (unsigned)v0;
+            mt[64 + l] = (unsigned)v1;
+            mt[128 + l] = (unsigned)v2;
+            mt[192 + l] = (unsigned)v3;
+            mt[256 + l] = (unsigned)v4;
+            mt[320 + l] = (unsigned)v5;
+            mt[384 + l] = (unsigned)v6;
+            mt[448 + l] = (unsigned)v7;
+            mt[512 + l] = (unsigned)v8;
+            if (576 + l < kMtN) mt[576 + l] = (unsigned)v9;
+        }
+    }
+    lds_barrier();
+    if (wv == 1) span_end(0, 1);
+    // One twist per 624-word block, as k_prepare: lane k < 227 computes words k, k + 227, k + 454.
+    // One barrier between two blocks (none behind the last: its words only go to memory).  The
+    // new state goes to LDS first; tempering and the stores to R follow behind the barrier, beside
+    // the next block's LDS reads, off the chain from one block to the next.
+    const int nb = io.nb;
+    unsigned *cur = mt, *nxt = mt2;
+    for (int blk = 0; blk < nb; ++blk) {
+        unsigned *dst = d.R() + (size_t)t * io.W + (size_t)blk * kMtN;
+        unsigned n0 = 0, n1 = 0, n2 = 0;
+        if (k < 227) {
+            n0 = cur[k + 397] ^ mt_twist(cur[k], cur[k + 1]);
+            n1 = n0 ^ mt_twist(cur[k + 227], cur[k + 228]);
+            nxt[k] = n0;
+            nxt[k + 227] = n1;
+            if (k < kMtN - 454) {
+                const unsigned nx = (k + 455 < kMtN) ? cur[k + 455] : (cur[397] ^ mt_twist(cur[0], cur[1]));
+                n2 = n1 ^ mt_twist(cur[k + 454], nx);
+                nxt[k + 454] = n2;
+            }
+        }
+        if (blk + 1 < nb) lds_barrier();
+        if (k < 227) {
+            dst[k] = mt_temper(n0);
+            dst[k + 227] = mt_temper(n1);
+            if (k < kMtN - 454) dst[k + 454] = mt_temper(n2);
+        }
+        unsigned *tmp = cur;
+        cur = nxt;
+        nxt = tmp;
+    }
+    if (wv == 1) span_end(0, 2);
+}
+
 // mz_create's device initialisation in one launch (instead of three copies and three memsets,
 // each a synchronous runtime call): the Params block, the seed word, the lambda powers (the float
 // chain lp[k] = lp[k - 1] * lam of utils.cpp:25-27, on one thread, in the order the host ran it),
@@ -6333,6 +6589,8 @@ struct mz_batch {
     int chain3_nc = 0;         // k_chain3 node class (64 .. 1024) for K = 1 trees, 0: k_chain / k_step
     bool chain3_w4 = false;    // k_chain3 with the draw wave (four waves; mz_create)
     ChainK chain_k{};          // k_chain3's copy of the Params fields its waves read (mz_create)
+    bool prep1 = false;        // mz_prepare / mz_prepare_select launch k_prepare1 (mz_create)
+    Prep1IO prep1_io{};        // its argument line but for the call's own fields (mz_create)
     int tree_nc = -1;          // k_tree node class for 2 <= K <= 64 trees (-1: k_step)
     bool hbm = false;          // the pool's LDS image exceeds a CU's LDS: every step launch is k_hbm
     bool seed_ref = false;     // holds a reference on its device's seeding table (seed_table)
@@ -7349,6 +7607,11 @@ int mz_create(int B, int N, int A, int K, int S, float delta_lb, uint32_t seed, 
                    &seed_cp, &seed_cp_n);
     b->seed_ref = seed_cp != nullptr;
     const Params host_params{b->geo, b->dev, seed_cp, seed_cp_n};
+    // k_prepare1: one root expansion of one draw, one lane per action (P and PS packed in 16 bits
+    // each: S <= 65000).  MZ_PREPARE_GENERAL keeps k_prepare (A/B runs, the tests of both).
+    b->prep1 = N == 1 && K == 1 && A <= kMaxActions && b->P < 65536 && b->PS < 65536 && !getenv_flag("MZ_PREPARE_GENERAL");
+    b->prep1_io = Prep1IO{nullptr, nullptr, nullptr, seed_cp, seed_cp_n, g.W, g.root_offset, 0.f, g.one_minus_rho,
+                          d.o_R, d.o_D, g.W / kMtN};
     // k_chain3 takes these as launch arguments: fixed from here on, as the Params block they mirror
     b->chain_k = ChainK{g.one_minus_rho, g.W, d.o_R, d.o_err, d.o_D, d.o_stats, g.delta, d.o_pb, d.o_sq, 0};
     assert(b->chain_k.one_minus_rho == host_params.g.one_minus_rho && b->chain_k.W == host_params.g.W &&
@@ -7479,6 +7742,24 @@ int mz_synchronize(mz_batch *b) {
     return check_device_errors(b);
 }
 
+namespace {
+// the handle's prepare kernel (mz_create: k_prepare1 for K = 1 single-agent handles of A <= 64)
+void launch_prepare(mz_batch *b, const PrepArgs &a, size_t jl) {
+    if (b->prep1) {
+        Prep1IO io = b->prep1_io;
+        io.idx_x = a.idx_x;
+        io.idy = a.idy;
+        io.act = a.act;
+        io.eps = a.eps;
+        const int bak = b->B | (b->A << 24), pps = b->P | (b->PS << 16);
+        hipLaunchKernelGGL(k_prepare1, dim3(b->B), dim3(kPrep1Waves * kWave), 0, b->stream, (char *)b->dev.base,
+                           a.reward, a.value, a.policy, a.beta, a.noise, bak, pps, io);
+        return;
+    }
+    hipLaunchKernelGGL(k_prepare, dim3(b->B), dim3(256), jl, b->stream, b->prm, a);
+}
+}  // namespace
+
 int mz_prepare(mz_batch *b, const float *rewards, const float *values, const float *policy, const float *beta, int K,
                float noise_eps, const float *noises, int mem) {
     if (!b) return fail(MZ_ERR_ARG, "null handle");
@@ -7516,7 +7797,7 @@ int mz_prepare(mz_batch *b, const float *rewards, const float *values, const flo
     a.idx_x = a.idy = a.act = nullptr;
     const size_t jl = (b->N > 1) ? (size_t)((12 * b->NA + 15) & ~15) + 8 * (size_t)b->NA + 4 * (size_t)kWave * b->N : 0;
     b->dirty = true;
-    hipLaunchKernelGGL(k_prepare, dim3(b->B), dim3(256), jl, b->stream, b->prm, a);
+    launch_prepare(b, a, jl);
     HIP_TRY(hipGetLastError());
     b->rb_valid = b->rb_dev_valid = false;
     b->prepared = true;
@@ -7555,7 +7836,7 @@ int mz_prepare_select(mz_batch *b, const float *rewards, const float *values, co
     a.idy = idy;
     a.act = actions;
     b->dirty = true;
-    hipLaunchKernelGGL(k_prepare, dim3(b->B), dim3(256), 0, b->stream, b->prm, a);
+    launch_prepare(b, a, 0);
     HIP_TRY(hipGetLastError());
     b->rb_valid = b->rb_dev_valid = false;
     b->prepared = true;
@@ -7733,6 +8014,12 @@ int mz_fused_kernel(mz_batch *b, char *out, int len) {
 int mz_fused_waves(mz_batch *b, int *waves) {
     if (!b || !waves) return fail(MZ_ERR_ARG, "mz_fused_waves: null argument");
     *waves = b->chain3_nc > 0 ? (b->chain3_w4 ? 4 : 3) : 0;
+    return MZ_OK;
+}
+
+int mz_prepare_kernel(mz_batch *b, char *out, int len) {
+    if (!b || !out || len < 1) return fail(MZ_ERR_ARG, "mz_prepare_kernel: null argument");
+    std::snprintf(out, (size_t)len, "%s", b->prep1 ? "k_prepare1" : "k_prepare");
     return MZ_OK;
 }
 

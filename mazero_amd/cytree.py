@@ -466,6 +466,13 @@ class Tree_batch:
         check(self._lib, self._lib.mz_fused_waves(self._h, C.byref(n)), "fused_waves")
         return int(n.value)
 
+    def prepare_kernel(self) -> str:
+        """Name of the kernel this handle launches for prepare / prepare_selection ("k_prepare1":
+        the role-specialised K = 1 kernel, or "k_prepare"): include/mzdriver.h mz_prepare_kernel."""
+        buf = C.create_string_buffer(48)
+        check(self._lib, self._lib.mz_prepare_kernel(self._h, buf, len(buf)), "prepare_kernel")
+        return buf.value.decode()
+
     def synchronize(self):
         self._sync_stream()
         check(self._lib, self._lib.mz_synchronize(self._h), "synchronize")
