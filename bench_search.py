@@ -13,6 +13,10 @@ Reported, as one JSON line:
   inverse support transforms of every simulation in one launch (mz_inverse_transform) instead of the
   model's torch ops. Same network and seeds; `actions_equal_device` says whether one environment
   step's sampled actions and visit counts equal the `device` loop's.
+- `device_later_cache`: `device_fused_transforms` with `later_action_cache=True` as well: the later
+  agents' greedy actions of every simulation come from a per-node cache (mz_policy_glue_later,
+  mz_joint_action_cached) instead of a prediction pass on the selected leaves. Its own
+  `actions_equal_device`, and the recorded graphs' node counts per agent without and with the cache.
 - `device_eager`: the same driver without graphs.
 - `selfplay_step_host_consumers` / `selfplay_step_device_consumers`: a whole self-play step with
   its per-root decisions (select_action, epsilon-greedy, recorded policy probability,
@@ -114,6 +118,24 @@ def main():
         all(np.array_equal(x, y) for x, y in zip(a.sampled_visit_count, b.sampled_visit_count))
     line["device_fused_transforms"] = {"value": round(sims_per_step / t, 1), "ms_per_step": round(t * 1e3, 3),
                                        "actions_equal_device": bool(same_actions)}
+    # the fused loop with the later agents' greedy actions from the per-node cache (mz_policy_glue_later,
+    # mz_joint_action_cached) instead of a prediction pass on the leaves: again the same searches
+    t = timed(SampledMCTS(cfg, np.random.RandomState(0), use_graph=True, fused_transforms=True,
+                          later_action_cache=True), args.steps, 2)
+    c = env_step(SampledMCTS(cfg, np.random.RandomState(5), use_graph=True, fused_transforms=True,
+                             later_action_cache=True), 0)
+    same_actions = all(np.array_equal(x, y) for x, y in zip(a.sampled_actions, c.sampled_actions)) and \
+        all(np.array_equal(x, y) for x, y in zip(a.sampled_visit_count, c.sampled_visit_count))
+    from mazero_amd.mcts_sampled import _LOOPS
+
+    # recorded graph nodes per agent of the fused loops, without and with the cache (a loop's key holds
+    # the agent at [4], fused_transforms at [-3] and later_action_cache at [-1])
+    nodes = {flag: [v.graph_nodes[0] for k, v in sorted(_LOOPS.items(), key=lambda kv: kv[0][4])
+                    if k[-3] is not None and k[-1] is flag and v.graph_nodes] for flag in (False, True)}
+    line["device_later_cache"] = {"value": round(sims_per_step / t, 1), "ms_per_step": round(t * 1e3, 3),
+                                  "actions_equal_device": bool(same_actions),
+                                  "graph_nodes_per_agent": {"fused_transforms": nodes[False],
+                                                            "later_cache": nodes[True]}}
     if args.device_only:
         line["steps"] = args.steps
         print(json.dumps(line), flush=True)

@@ -130,6 +130,42 @@ int mz_root_glue_wide(mz_batch *b, const void *logits, int dtype, int64_t row_st
 int mz_joint_action_wide(mz_batch *b, const void *pred_logits, int dtype, int num_agents, int current_agent,
                          const int32_t *factor, int factor_cols, const int32_t *actions, int64_t *joint_out);
 
+/* The later agents' greedy actions as a property of the node (mcts_sampled.py:136-147).  For every
+ * agent after the current one the reference runs the prediction network on the selected leaf's parent
+ * state only to take np.argmax of its logits; that state is the row of next_h an earlier simulation
+ * produced, on which the network already ran.  With a prediction that is a deterministic, row-wise
+ * function of the state, those actions are computed once, when the node's state is produced, and
+ * looked up by the selection's hidden_state_index_x.
+ *
+ * mz_policy_glue_later: mz_policy_glue of the current agent and the later agents' argmax in one
+ * launch, one wave per (root, role).
+ * logits: [B, num_agents, A] of dtype `dtype`, row stride `row_stride` >= num_agents * A elements.
+ * probs_out, beta_out: float32 [B, A], the bytes of mz_policy_glue(..., col_offset = current_agent * A,
+ * ...) (of mz_policy_glue_wide for A > 64).  Both NULL: only the later agents are computed (the root's
+ * slot); exactly one NULL is MZ_ERR_ARG.
+ * later_out: int32 [B, num_agents]; column k > current_agent receives np.argmax(logits[i, k, :]) (first
+ * maximum, first NaN wins, as mz_joint_action); columns <= current_agent are not written.  May be NULL
+ * when current_agent == num_agents - 1: the call then equals mz_policy_glue.
+ * Any action_space_size the handle has (1..255): one lane per action up to 64, the tiles of the _wide
+ * entry points above.  Nothing is allocated or uploaded, so the call can be captured in a graph. */
+int mz_policy_glue_later(mz_batch *b, const void *logits, int dtype, int64_t row_stride, int num_agents,
+                         int current_agent, double sampled_tau, float *probs_out, float *beta_out,
+                         int32_t *later_out);
+
+/* mz_joint_action with the later agents' actions read from the per-node cache that
+ * mz_policy_glue_later filled (mcts_sampled.py:116-147):
+ *   joint[i, k] = factor[i, k]                      for k <  current_agent
+ *   joint[i, k] = actions[i]                        for k == current_agent
+ *   joint[i, k] = later_pool[idx_x[i]][i][k]        for k >  current_agent
+ * later_pool: int32 [slots, B, num_agents], slot s the later_out of the node whose
+ * hidden_state_index_x is s; idx_x: int32 [B], the selection's hidden_state_index_x.  An idx_x[i]
+ * outside [0, slots) reads slot 0: the kernel never reads outside the pool (the joint action indexes an
+ * embedding in the model).  factor, actions, joint_out as mz_joint_action.  Any action_space_size;
+ * nothing is allocated or uploaded. */
+int mz_joint_action_cached(mz_batch *b, const int32_t *later_pool, int slots, const int32_t *idx_x,
+                           int num_agents, int current_agent, const int32_t *factor, int factor_cols,
+                           const int32_t *actions, int64_t *joint_out);
+
 /* Inverse support transform of the value and the reward head of one simulation: what
  * MAMuZeroNet.recurrent_inference applies to the two heads' logits in eval mode
  * (config/smac/model.py:562-572; core/config.py:430-499: softmax, _inv_phi, _inv_h), both heads in

@@ -119,6 +119,11 @@ DRIVER_SIGNATURES = {
     "mz_policy_glue_wide": (_i, [_p, _p, _i, _i64, _i64, C.c_double, _p, _p]),
     "mz_root_glue_wide": (_i, [_p, _p, _i, _i64, _i64, _p, _i64, _p, C.c_double, C.c_double, _p, _p, _p]),
     "mz_joint_action_wide": (_i, [_p, _p, _i, _i, _i, _p, _i, _p, _p]),
+    # the later agents' greedy actions per node: (handle, logits, dtype, row_stride, num_agents,
+    # current_agent, sampled_tau, probs_out, beta_out, later_out) and (handle, later_pool, slots, idx_x,
+    # num_agents, current_agent, factor, factor_cols, actions, joint_out)
+    "mz_policy_glue_later": (_i, [_p, _p, _i, _i64, _i, _i, C.c_double, _p, _p, _p]),
+    "mz_joint_action_cached": (_i, [_p, _p, _i, _p, _i, _i, _p, _i, _p, _p]),
     # (handle or NULL, stream, stage, n, value head: in, dtype, stride, lo, hi; reward head likewise; outputs)
     "mz_inverse_transform": (_i, [_p, _p, _i, _i, _p, _i, _i64, _i, _i, _p, _i, _i64, _i, _i, _p, _p]),
     "mz_inverse_transform_wide": (_i, [_p, _p, _i, _i, _p, _i, _i64, _i, _i, _p, _i, _i64, _i, _i, _p, _p]),

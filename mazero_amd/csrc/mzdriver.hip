@@ -145,15 +145,12 @@ int pow_mode(double inv) {
     return inv == 1.0 ? 0 : inv == 2.0 ? kPowSquare : inv == 0.5 ? kPowSqrt : kPowGeneral;
 }
 
-// mcts_sampled.py:158-161 (+ .astype(np.float32), :169-170) for root blockIdx.x.
+// mcts_sampled.py:158-161 (+ .astype(np.float32), :169-170) for root t, lane l of its wave: the body
+// of k_policy_glue and of role 0 of k_policy_glue_later (lds[kWave] and acc[9] are the workgroup's).
 template <bool F16>
-__global__ __launch_bounds__(kWave) void k_policy_glue(const void *logits, long long row_stride, long long col_off,
-                                                       int A, int use_pow, float tau_inv, float *probs,
-                                                       float *beta, const unsigned short *hexp) {
-    __shared__ float lds[kWave];
-    __shared__ float acc[9];
-    const int t = blockIdx.x;
-    const int l = threadIdx.x;
+__device__ __forceinline__ void policy_glue_row(const void *logits, long long row_stride, long long col_off, int A,
+                                                int use_pow, float tau_inv, float *probs, float *beta,
+                                                const unsigned short *hexp, int t, int l, float *lds, float *acc) {
     const bool on = l < A;
     const float x = on ? load_elem<F16>(logits, (long long)t * row_stride + col_off + l) : -INFINITY;
     // np.max(..., axis=-1): NaN propagates
@@ -171,6 +168,28 @@ __global__ __launch_bounds__(kWave) void k_policy_glue(const void *logits, long 
         probs[(long long)t * A + l] = p;
         beta[(long long)t * A + l] = b;
     }
+}
+
+template <bool F16>
+__global__ __launch_bounds__(kWave) void k_policy_glue(const void *logits, long long row_stride, long long col_off,
+                                                       int A, int use_pow, float tau_inv, float *probs,
+                                                       float *beta, const unsigned short *hexp) {
+    __shared__ float lds[kWave];
+    __shared__ float acc[9];
+    policy_glue_row<F16>(logits, row_stride, col_off, A, use_pow, tau_inv, probs, beta, hexp, blockIdx.x,
+                         threadIdx.x, lds, acc);
+}
+
+// np.argmax of the row of A <= 64 elements that starts at element `row` (mcts_sampled.py:136-145): the
+// first NaN if the row holds one, else the first maximum; the result in every lane of the wave.
+template <bool F16>
+__device__ __forceinline__ int np_argmax_row(const void *p, long long row, int A, int l) {
+    const bool on = l < A;
+    const float v = on ? load_elem<F16>(p, row + l) : -INFINITY;
+    const unsigned long long nan_mask = __ballot(on && (v != v));
+    if (nan_mask) return __ffsll((long long)nan_mask) - 1;  // (wave-uniform)
+    const float m = wave_max(v);
+    return __ffsll((long long)__ballot(on && v == m)) - 1;
 }
 
 // float64 -> float16 with one rounding (round to nearest, ties to even), as numpy casts a float64
@@ -283,18 +302,57 @@ __global__ __launch_bounds__(kWave) void k_joint_action(const void *pred, int N,
     if (l < N && l <= cur) joint[(long long)t * N + l] = (l < cur) ? (long long)factor[(long long)t * fcols + l]
                                                                     : (long long)actions[t];
     for (int k = cur + 1; k < N; ++k) {
-        const bool on = l < A;
-        const float v = on ? load_elem<F16>(pred, ((long long)t * N + k) * A + l) : -INFINITY;
-        const unsigned long long nan_mask = __ballot(on && (v != v));
-        int idx;
-        if (nan_mask) {
-            idx = __ffsll((long long)nan_mask) - 1;
-        } else {
-            const float m = wave_max(v);
-            idx = __ffsll((long long)__ballot(on && v == m)) - 1;
-        }
+        const int idx = np_argmax_row<F16>(pred, ((long long)t * N + k) * A, A, l);
         if (l == 0) joint[(long long)t * N + k] = idx;
     }
+}
+
+// mz_policy_glue_later: one wave per (root, role), grid (B, roles).  Role 0 is the policy glue of the
+// current agent (absent when the caller wants the later agents only: then `glue` is 0 and every role
+// is an argmax); role j >= 1 is np.argmax of agent cur + j's logits into later[t, cur + j].  The role
+// is the workgroup's, so the ballots and wave_max of either body stay in wave-uniform control flow.
+constexpr int kMaxLaterAgents = 65535;  // a role per agent in grid.y
+template <bool F16>
+__global__ __launch_bounds__(kWave) void k_policy_glue_later(const void *logits, long long row_stride, int N, int A,
+                                                             int cur, int glue, int use_pow, float tau_inv,
+                                                             float *probs, float *beta, int *later,
+                                                             const unsigned short *hexp) {
+    __shared__ float lds[kWave];
+    __shared__ float acc[9];
+    const int t = blockIdx.x;
+    const int l = threadIdx.x;
+    const int j = (int)blockIdx.y + 1 - glue;
+    if (j == 0) {
+        policy_glue_row<F16>(logits, row_stride, (long long)cur * A, A, use_pow, tau_inv, probs, beta, hexp, t, l,
+                             lds, acc);
+        return;
+    }
+    const int k = cur + j;
+    const int idx = np_argmax_row<F16>(logits, (long long)t * row_stride + (long long)k * A, A, l);
+    if (l == 0) later[(long long)t * N + k] = idx;
+}
+
+// mz_joint_action_cached: one thread per (root i, agent k); the later agents' actions are those the
+// node selected for root i (its hidden_state_index_x, idx_x[i]) got from mz_policy_glue_later.
+constexpr int kCachedLanes = 256;
+__global__ __launch_bounds__(kCachedLanes) void k_joint_action_cached(const int *pool, int slots, const int *idx_x,
+                                                                      int B, int N, int cur, const int *factor,
+                                                                      int fcols, const int *actions,
+                                                                      long long *joint) {
+    const long long e = (long long)blockIdx.x * kCachedLanes + threadIdx.x;
+    if (e >= (long long)B * N) return;
+    const int i = (int)(e / N), k = (int)(e % N);
+    long long v;
+    if (k < cur) {
+        v = factor[(long long)i * fcols + k];
+    } else if (k == cur) {
+        v = actions[i];
+    } else {
+        int s = idx_x[i];
+        if (s < 0 || s >= slots) s = 0;  // (never outside the pool: the joint action feeds an embedding)
+        v = pool[((long long)s * B + i) * N + k];
+    }
+    joint[e] = v;
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -403,15 +461,13 @@ __device__ __forceinline__ float np_sub_max(float x, float m) {
     return x - m;
 }
 
-// k_policy_glue for 64 < A <= 255
+// policy_glue_row for 64 < A <= 255: the body of k_policy_glue_wide and of role 0 of
+// k_policy_glue_later_wide (lds[kWideRow] is the workgroup's)
 template <bool F16, int T>
-__global__ __launch_bounds__(kWave) void k_policy_glue_wide(const void *logits, long long row_stride,
-                                                            long long col_off, int A, SumPlan plan, int use_pow,
-                                                            float tau_inv, float *probs, float *beta,
-                                                            const unsigned short *hexp) {
-    __shared__ float lds[kWideRow];
-    const int t = blockIdx.x;
-    const int l = threadIdx.x;
+__device__ __forceinline__ void policy_glue_row_wide(const void *logits, long long row_stride, long long col_off,
+                                                     int A, SumPlan plan, int use_pow, float tau_inv, float *probs,
+                                                     float *beta, const unsigned short *hexp, int t, int l,
+                                                     float *lds) {
     float x[T], e[T], p[T], q[T];
 #pragma unroll
     for (int j = 0; j < T; ++j) {
@@ -436,6 +492,17 @@ __global__ __launch_bounds__(kWave) void k_policy_glue_wide(const void *logits, 
             beta[(long long)t * A + a] = round_as<F16>(q[j] / s2);
         }
     }
+}
+
+// k_policy_glue for 64 < A <= 255
+template <bool F16, int T>
+__global__ __launch_bounds__(kWave) void k_policy_glue_wide(const void *logits, long long row_stride,
+                                                            long long col_off, int A, SumPlan plan, int use_pow,
+                                                            float tau_inv, float *probs, float *beta,
+                                                            const unsigned short *hexp) {
+    __shared__ float lds[kWideRow];
+    policy_glue_row_wide<F16, T>(logits, row_stride, col_off, A, plan, use_pow, tau_inv, probs, beta, hexp,
+                                 blockIdx.x, threadIdx.x, lds);
 }
 
 // k_root_glue for 64 < A <= 255
@@ -501,9 +568,35 @@ __global__ __launch_bounds__(kWave) void k_root_glue_wide(const void *logits, lo
     }
 }
 
-// k_joint_action for 64 < A <= 255.  np.argmax: the smallest action holding a NaN if there is one,
-// else the smallest action equal to the maximum.  Action l + 64 j orders by tile first, so the
-// tiles are scanned in order and the first set ballot bit taken inside a tile.
+// np_argmax_row for 64 < A <= 255 (k_joint_action_wide, k_policy_glue_later_wide).  np.argmax: the
+// smallest action holding a NaN if there is one, else the smallest action equal to the maximum.
+// Action l + 64 j orders by tile first, so the tiles are scanned in order and the first set ballot bit
+// taken inside a tile.
+template <bool F16, int T>
+__device__ __forceinline__ int np_argmax_row_wide(const void *p, long long row, int A, int l) {
+    float v[T];
+    float m = -INFINITY;
+    int idx = -1;
+#pragma unroll
+    for (int j = 0; j < T; ++j) {
+        const int a = l + kWave * j;
+        const bool on = a < A;
+        v[j] = on ? load_elem<F16>(p, row + a) : -INFINITY;
+        m = fmaxf(m, v[j]);
+        const unsigned long long nan_mask = __ballot(on && (v[j] != v[j]));
+        if (idx < 0 && nan_mask) idx = kWave * j + __ffsll((long long)nan_mask) - 1;
+    }
+    if (idx < 0) {  // (wave-uniform)
+        m = wave_max(m);
+#pragma unroll
+        for (int j = 0; j < T; ++j) {
+            const unsigned long long hit = __ballot(l + kWave * j < A && v[j] == m);
+            if (idx < 0 && hit) idx = kWave * j + __ffsll((long long)hit) - 1;
+        }
+    }
+    return idx;
+}
+
 template <bool F16, int T>
 __global__ __launch_bounds__(kWave) void k_joint_action_wide(const void *pred, int N, int A, int cur,
                                                              const int *factor, int fcols, const int *actions,
@@ -513,28 +606,30 @@ __global__ __launch_bounds__(kWave) void k_joint_action_wide(const void *pred, i
     if (l < N && l <= cur) joint[(long long)t * N + l] = (l < cur) ? (long long)factor[(long long)t * fcols + l]
                                                                     : (long long)actions[t];
     for (int k = cur + 1; k < N; ++k) {
-        float v[T];
-        float m = -INFINITY;
-        int idx = -1;
-#pragma unroll
-        for (int j = 0; j < T; ++j) {
-            const int a = l + kWave * j;
-            const bool on = a < A;
-            v[j] = on ? load_elem<F16>(pred, ((long long)t * N + k) * A + a) : -INFINITY;
-            m = fmaxf(m, v[j]);
-            const unsigned long long nan_mask = __ballot(on && (v[j] != v[j]));
-            if (idx < 0 && nan_mask) idx = kWave * j + __ffsll((long long)nan_mask) - 1;
-        }
-        if (idx < 0) {  // (wave-uniform)
-            m = wave_max(m);
-#pragma unroll
-            for (int j = 0; j < T; ++j) {
-                const unsigned long long hit = __ballot(l + kWave * j < A && v[j] == m);
-                if (idx < 0 && hit) idx = kWave * j + __ffsll((long long)hit) - 1;
-            }
-        }
+        const int idx = np_argmax_row_wide<F16, T>(pred, ((long long)t * N + k) * A, A, l);
         if (l == 0) joint[(long long)t * N + k] = idx;
     }
+}
+
+// k_policy_glue_later for 64 < A <= 255
+template <bool F16, int T>
+__global__ __launch_bounds__(kWave) void k_policy_glue_later_wide(const void *logits, long long row_stride, int N,
+                                                                  int A, int cur, int glue, SumPlan plan,
+                                                                  int use_pow, float tau_inv, float *probs,
+                                                                  float *beta, int *later,
+                                                                  const unsigned short *hexp) {
+    __shared__ float lds[kWideRow];
+    const int t = blockIdx.x;
+    const int l = threadIdx.x;
+    const int j = (int)blockIdx.y + 1 - glue;
+    if (j == 0) {
+        policy_glue_row_wide<F16, T>(logits, row_stride, (long long)cur * A, A, plan, use_pow, tau_inv, probs, beta,
+                                     hexp, t, l, lds);
+        return;
+    }
+    const int k = cur + j;
+    const int idx = np_argmax_row_wide<F16, T>(logits, (long long)t * row_stride + (long long)k * A, A, l);
+    if (l == 0) later[(long long)t * N + k] = idx;
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -978,6 +1073,84 @@ static int joint_action(const char *fn, bool wide, mz_batch *b, const void *pred
         hipLaunchKernelGGL(k_joint_action<false>, dim3(B), dim3(kWave), 0, stream, pred_logits, num_agents, A,
                            current_agent, (const int *)factor, factor_cols, (const int *)actions,
                            (long long *)joint_out);
+    mz_internal_enqueued(b);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return mz_internal_fail(MZ_ERR_DEVICE, hipGetErrorString(e));
+    return MZ_OK;
+}
+
+int mz_policy_glue_later(mz_batch *b, const void *logits, int dtype, int64_t row_stride, int num_agents,
+                         int current_agent, double sampled_tau, float *probs_out, float *beta_out,
+                         int32_t *later_out) {
+    const char *fn = "mz_policy_glue_later";
+    int B = 0, A = 0;
+    hipStream_t stream = nullptr;
+    int rc = mz_internal_launch_info(b, &B, &A, &stream);
+    if (rc) return rc;
+    SumPlan plan{};
+    if (A > kWave && !sum_plan(A, &plan)) return glue_fail(MZ_ERR_UNSUPPORTED, fn, "action_space_size > 255");
+    if (num_agents < 1 || num_agents > kMaxLaterAgents || current_agent < 0 || current_agent >= num_agents)
+        return glue_fail(MZ_ERR_ARG, fn, "bad agent index / count");
+    if (!logits) return glue_fail(MZ_ERR_ARG, fn, "null buffer");
+    if (!probs_out != !beta_out) return glue_fail(MZ_ERR_ARG, fn, "probs_out and beta_out go together");
+    const int glue = probs_out ? 1 : 0, later = num_agents - 1 - current_agent;
+    if (later > 0 && !later_out) return glue_fail(MZ_ERR_ARG, fn, "later_out required for later agents");
+    if (glue + later == 0) return glue_fail(MZ_ERR_ARG, fn, "no output asked for");
+    if (dtype != MZ_DT_F32 && dtype != MZ_DT_F16) return glue_fail(MZ_ERR_ARG, fn, "bad dtype");
+    if (row_stride < (int64_t)num_agents * A)
+        return glue_fail(MZ_ERR_ARG, fn, "logits row does not hold every agent's actions");
+    if (!(sampled_tau > 0.0)) return glue_fail(MZ_ERR_ARG, fn, "sampled_tau must be > 0");
+    const double inv = 1.0 / sampled_tau;  // as mz_policy_glue
+    const float tau_inv = (dtype == MZ_DT_F16) ? (float)(_Float16)inv : (float)inv;
+    const int use_pow = pow_mode(inv);
+    const unsigned short *hexp = half_exp_table();
+    const dim3 grid(B, glue + later);
+    if (A > kWave) {
+#define MZ_LAUNCH(T)                                                                                              \
+    if (dtype == MZ_DT_F16)                                                                                       \
+        hipLaunchKernelGGL((k_policy_glue_later_wide<true, T>), grid, dim3(kWave), 0, stream, logits,             \
+                           (long long)row_stride, num_agents, A, current_agent, glue, plan, use_pow, tau_inv,     \
+                           probs_out, beta_out, (int *)later_out, hexp);                                          \
+    else                                                                                                          \
+        hipLaunchKernelGGL((k_policy_glue_later_wide<false, T>), grid, dim3(kWave), 0, stream, logits,            \
+                           (long long)row_stride, num_agents, A, current_agent, glue, plan, use_pow, tau_inv,     \
+                           probs_out, beta_out, (int *)later_out, hexp)
+        MZ_WIDE_TILES(A, MZ_LAUNCH);
+#undef MZ_LAUNCH
+    } else if (dtype == MZ_DT_F16)
+        hipLaunchKernelGGL(k_policy_glue_later<true>, grid, dim3(kWave), 0, stream, logits, (long long)row_stride,
+                           num_agents, A, current_agent, glue, use_pow, tau_inv, probs_out, beta_out,
+                           (int *)later_out, hexp);
+    else
+        hipLaunchKernelGGL(k_policy_glue_later<false>, grid, dim3(kWave), 0, stream, logits, (long long)row_stride,
+                           num_agents, A, current_agent, glue, use_pow, tau_inv, probs_out, beta_out,
+                           (int *)later_out, hexp);
+    mz_internal_enqueued(b);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return mz_internal_fail(MZ_ERR_DEVICE, hipGetErrorString(e));
+    return MZ_OK;
+}
+
+int mz_joint_action_cached(mz_batch *b, const int32_t *later_pool, int slots, const int32_t *idx_x, int num_agents,
+                           int current_agent, const int32_t *factor, int factor_cols, const int32_t *actions,
+                           int64_t *joint_out) {
+    const char *fn = "mz_joint_action_cached";
+    int B = 0, A = 0;
+    hipStream_t stream = nullptr;
+    int rc = mz_internal_launch_info(b, &B, &A, &stream);
+    if (rc) return rc;
+    if (num_agents < 1 || num_agents > kMaxLaterAgents || current_agent < 0 || current_agent >= num_agents)
+        return glue_fail(MZ_ERR_ARG, fn, "bad agent index / count");
+    if (!actions || !joint_out) return glue_fail(MZ_ERR_ARG, fn, "null buffer");
+    if (current_agent > 0 && (!factor || factor_cols < current_agent))
+        return glue_fail(MZ_ERR_ARG, fn, "factor must hold the previous agents' actions");
+    if (current_agent + 1 < num_agents && (!later_pool || !idx_x || slots < 1))
+        return glue_fail(MZ_ERR_ARG, fn, "later-action pool and idx_x required for later agents");
+    const long long n = (long long)B * num_agents;
+    hipLaunchKernelGGL(k_joint_action_cached, dim3((unsigned)((n + kCachedLanes - 1) / kCachedLanes)),
+                       dim3(kCachedLanes), 0, stream, (const int *)later_pool, slots, (const int *)idx_x, B,
+                       num_agents, current_agent, (const int *)factor, factor_cols, (const int *)actions,
+                       (long long *)joint_out);
     mz_internal_enqueued(b);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return mz_internal_fail(MZ_ERR_DEVICE, hipGetErrorString(e));

@@ -17,7 +17,9 @@ and the per-simulation glue stay on the device:
 of 65..255; with `fused_transforms`: the inverse transforms of the value and reward heads are one
 mz_inverse_transform launch, torch's arithmetic on this device restated bit for bit, instead of the
 model's ~46 torch kernels; with `wide_supports` as well, mz_inverse_transform_wide does the same for
-supports of 65..1024 elements)
+supports of 65..1024 elements; with `later_action_cache`: the `model.prediction(leaf)` pass goes, the
+later agents' argmax is taken once per node by mz_policy_glue_later, which also does the policy glue,
+and the joint action reads it back through mz_joint_action_cached)
 
 so a search has no host synchronisation between `prepare` and the final readback.  The root
 preprocessing (mcts_sampled.py:51-106) is split: the host draws from `np_random` (the Dirichlet
@@ -119,8 +121,19 @@ class _SearchLoop:
     memory (mz_reseed), so replaying the graph is a new search."""
 
     def __init__(self, tb, B, A, N, cur, hidden, dev, model, root_mode=None, wide=False, fused=None,
-                 wide_supports=False):
+                 wide_supports=False, later_slots=0):
         self.tb, self.B, self.A, self.N, self.cur, self.dev = tb, B, A, N, cur, dev
+        # later_slots = S + 1 (SampledMCTS's later_action_cache; 0: off): the later agents' greedy actions
+        # of every node, slot hidden_state_index_x, filled by mz_policy_glue_later when the node's state
+        # is produced and read by mz_joint_action_cached instead of a prediction pass on the leaf.  The
+        # last agent has no later agents: its loop is the default one.
+        self.later = None
+        if later_slots and cur + 1 < N:
+            # (zeros: an action read before its slot was written would still index the model's embedding)
+            self.later = torch.zeros(later_slots, B, N, dtype=torch.int32, device=dev)
+            # the first search also takes the default path and compares the two joint actions
+            self.joint_cached = torch.empty(B, N, dtype=torch.int64, device=dev)
+            self.mismatch = torch.zeros((), dtype=torch.bool, device=dev)
         # supports of 65 .. 1024 elements take LOGITS through mz_inverse_transform_wide (SampledMCTS's
         # wide_supports) instead of EXPECTATION behind torch's softmax, multiply and sum
         self.wide_supports = bool(wide_supports)
@@ -231,6 +244,10 @@ class _SearchLoop:
         tb.prepare_selection_device(r[0], r[1], r[2], r[3], K, eps, r[4], c2, c1, disc, out=self.sel)
         act = self.sel[2]
         leaf = self.root  # simulation 0 selects a child of every root: its parent is the root (slot 0)
+        # the later-action cache is checked on the loop's first search, which is always eager
+        checked = self.later is not None and self.runs == 0
+        if checked:
+            self.mismatch.zero_()
         # One autocast context around the whole loop, its cast cache on: each fp32 weight is cast to
         # float16 once per search instead of once per simulation (the reference enters autocast per
         # simulation, mcts_sampled.py:150, so it casts every weight S times; the casts are identical).
@@ -238,20 +255,48 @@ class _SearchLoop:
         # Inside a caller's own autocast context the cache would outlive this loop (it is cleared
         # when the outermost context exits), so there the casts stay per simulation.
         with torch.autocast("cuda", cache_enabled=not torch.is_autocast_enabled("cuda")):
-            self._simulations(model, lib, h, leaf, act, B, A, N, cur, K, S, c2, c1, disc, tau)
+            self._simulations(model, lib, h, leaf, act, B, A, N, cur, K, S, c2, c1, disc, tau, checked)
+        if checked and bool(self.mismatch.item()):  # (the one host synchronisation, on a warm-up search)
+            warnings.warn(f"later_action_cache: the cached later agents' actions differ from those of "
+                          f"{type(model).__name__}.prediction on the selected leaves (prediction is not a "
+                          "deterministic row-wise function of the state); this search loop takes the default "
+                          "path", RuntimeWarning)
+            self.later = None  # for good: this search already ran on the default joint actions
 
-    def _simulations(self, model, lib, h, leaf, act, B, A, N, cur, K, S, c2, c1, disc, tau):
+    def _later_glue(self, lib, h, logits, tau, slot, glue=True):
+        """mz_policy_glue_later on `logits` [B, N, A]: the later agents' argmax into later[slot], with the
+        policy glue of the current agent into probs / beta unless `glue` is False (the root's slot)."""
+        logits = logits.contiguous()
+        check(lib, lib.mz_policy_glue_later(h, C.c_void_p(logits.data_ptr()), _dtype_code(logits),
+                                            logits.shape[1] * logits.shape[2], self.N, self.cur, float(tau),
+                                            C.c_void_p(self.probs.data_ptr()) if glue else None,
+                                            C.c_void_p(self.beta.data_ptr()) if glue else None,
+                                            C.c_void_p(self.later[slot].data_ptr())), "policy_glue_later")
+
+    def _simulations(self, model, lib, h, leaf, act, B, A, N, cur, K, S, c2, c1, disc, tau, checked=False):
         tb = self.tb
+        cached = self.later is not None
         for s in range(S):
-            if cur + 1 < N:  # later agents' actions from the leaf policy, :136-145
-                pred_logits, _ = model.prediction(leaf)
+            # later agents' actions from the leaf policy, :136-145: a prediction pass on the leaves, or
+            # (later_action_cache) the selected nodes' cached actions; the checked search runs both
+            ptr, dt = None, MZ_DT_F32
+            if cur + 1 < N and (checked or not cached or s == 0):
+                pred_logits, _ = model.prediction(leaf)  # (s == 0: the leaf batch is the root batch)
                 pred_logits = pred_logits.contiguous()
                 ptr, dt = C.c_void_p(pred_logits.data_ptr()), _dtype_code(pred_logits)
-            else:
-                ptr, dt = None, MZ_DT_F32
-            check(lib, self.joint_action(h, ptr, dt, N, cur, C.c_void_p(self.fac.data_ptr()),
-                                         self.fac.shape[1], C.c_void_p(act.data_ptr()),
-                                         C.c_void_p(self.joint.data_ptr())), "joint_action")
+                if cached and s == 0:
+                    self._later_glue(lib, h, pred_logits, tau, 0, glue=False)
+            if cached:
+                check(lib, lib.mz_joint_action_cached(
+                    h, C.c_void_p(self.later.data_ptr()), self.later.shape[0], C.c_void_p(self.sel[0].data_ptr()),
+                    N, cur, C.c_void_p(self.fac.data_ptr()), self.fac.shape[1], C.c_void_p(act.data_ptr()),
+                    C.c_void_p((self.joint_cached if checked else self.joint).data_ptr())), "joint_action_cached")
+            if checked or not cached:
+                check(lib, self.joint_action(h, ptr, dt, N, cur, C.c_void_p(self.fac.data_ptr()),
+                                             self.fac.shape[1], C.c_void_p(act.data_ptr()),
+                                             C.c_void_p(self.joint.data_ptr())), "joint_action")
+            if checked:  # dynamics takes the default joint action below: a mismatch costs nothing but the cache
+                self.mismatch |= (self.joint != self.joint_cached).any()
             r32 = v32 = None
             if self.fused is not None and getattr(model, "recurrent_inference_device", None) is None:
                 next_h, reward_logits = model.dynamics(leaf, self.joint)
@@ -284,11 +329,14 @@ class _SearchLoop:
                 if s == 0:
                     self.pool[0].copy_(self.root)
                 self.pool[s + 1].copy_(nh)  # :164
-            logits = logits.contiguous()
-            check(lib, self.policy_glue(h, C.c_void_p(logits.data_ptr()), _dtype_code(logits),
-                                        logits.shape[1] * logits.shape[2], cur * A, float(tau),
-                                        C.c_void_p(self.probs.data_ptr()), C.c_void_p(self.beta.data_ptr())),
-                  "policy_glue")
+            if cached:  # the policy glue, and the new node's later actions into its slot
+                self._later_glue(lib, h, logits, tau, s + 1)
+            else:
+                logits = logits.contiguous()
+                check(lib, self.policy_glue(h, C.c_void_p(logits.data_ptr()), _dtype_code(logits),
+                                            logits.shape[1] * logits.shape[2], cur * A, float(tau),
+                                            C.c_void_p(self.probs.data_ptr()), C.c_void_p(self.beta.data_ptr())),
+                      "policy_glue")
             if r32 is None:
                 r32 = reward.reshape(B).float()
                 v32 = value.reshape(B).float()
@@ -482,8 +530,21 @@ class SampledMCTS:
 
     def __init__(self, config, np_random: np.random.RandomState = None, *, lib=None, use_graph: bool = True,
                  root_shard: Tuple[int, int, int] = None, device_root: bool = True, wide_actions: bool = None,
-                 fused_transforms: bool = None, wide_supports: bool = None):
-        """`fused_transforms`: compute the inverse value / reward transforms of every simulation
+                 fused_transforms: bool = None, wide_supports: bool = None, later_action_cache: bool = None):
+        """`later_action_cache`: take the later agents' greedy actions of every simulation
+        (mcts_sampled.py:136-147) from a per-node cache instead of a `model.prediction` pass on the
+        selected leaves' parent states.  Such a state is row i of the `next_h` an earlier simulation
+        produced, and `prediction` already ran on it there; mz_policy_glue_later keeps the later agents'
+        argmax of those logits per node, and mz_joint_action_cached looks them up by the selection's
+        hidden_state_index_x.  This assumes that `prediction` is a deterministic, row-wise function of the
+        state (every net of the reference in eval mode is).  The assumption is checked on each loop's
+        first search, which also runs the default path and compares the joint actions on the device: on
+        a mismatch that search returns the default path's results, a RuntimeWarning names the model
+        class and the loop takes the default path from then on.  None reads
+        `config.later_action_cache` (False when the config has none).  The search of the last agent
+        has no later agents and is unchanged.
+
+        `fused_transforms`: compute the inverse value / reward transforms of every simulation
         (core/config.py:487-499) with one mz_inverse_transform launch instead of the model's
         `inverse_value_transform` / `inverse_reward_transform`; the search calls `model.dynamics` and
         `model.prediction` itself.  The supports are `config.value_support` / `config.reward_support`
@@ -539,6 +600,9 @@ class SampledMCTS:
         if wide_supports is None:
             wide_supports = getattr(config, "wide_supports", False)
         self.wide_supports = bool(wide_supports)
+        if later_action_cache is None:
+            later_action_cache = getattr(config, "later_action_cache", False)
+        self.later_action_cache = bool(later_action_cache)
         self.np_random = np.random if np_random is None else np_random
         self._lib = lib
         if root_shard is not None:
@@ -707,7 +771,7 @@ class SampledMCTS:
             # the discount is a kernel argument of the recorded launches
             key = (threading.get_ident(), id(tb), id(model), N, cur, float(eps), float(sampled_tau), float(disc),
                    tuple(hidden.shape), hidden.dtype, root_mode, self.wide_actions, self.fused_transforms,
-                   self.wide_supports)
+                   self.wide_supports, self.later_action_cache)
             with _LOCK:
                 for k in [k for k, v in _LOOPS.items() if v.model_ref() is None]:
                     del _LOOPS[k]  # loops (graph, pool) of models that no longer exist
@@ -718,7 +782,8 @@ class SampledMCTS:
                 if st is None or st.model_ref() is not model or st.storage != sig or st.tb is not tb:
                     st = _LOOPS[key] = _SearchLoop(tb, B, A, N, cur, hidden, dev, model, root_mode,
                                                    wide=self.wide_actions, fused=self.fused_transforms,
-                                                   wide_supports=self.wide_supports)
+                                                   wide_supports=self.wide_supports,
+                                                   later_slots=S + 1 if self.later_action_cache else 0)
                     st.storage = sig
                 _LOOPS.move_to_end(key)
                 while len(_LOOPS) > max(_MAX_LOOPS, 1):  # least recently used first

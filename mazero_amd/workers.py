@@ -63,10 +63,11 @@ def _device_reanalyze_decide(mcts, model, network_output, legal, policy_mask, de
     return reanalyze_policy_targets(mcts, model, network_output, legal, policy_mask, device)._asdict()
 
 
-def _default_mcts(config, np_random, root_shard, wide_actions=None):
+def _default_mcts(config, np_random, root_shard, wide_actions=None, later_action_cache=None):
     from .mcts_sampled import SampledMCTS
 
-    return SampledMCTS(config, np_random, root_shard=root_shard, wide_actions=wide_actions)
+    return SampledMCTS(config, np_random, root_shard=root_shard, wide_actions=wide_actions,
+                       later_action_cache=later_action_cache)
 
 
 @dataclass
@@ -86,9 +87,12 @@ class StepRecord:
 class _Shard:
     def __init__(self, model, config, total: int, *, seed: int, broadcaster=None, group=None, src: int = 0,
                  make_mcts: Optional[Callable] = None, device=None, rank: Optional[int] = None,
-                 world: Optional[int] = None, wide_actions: Optional[bool] = None):
+                 world: Optional[int] = None, wide_actions: Optional[bool] = None,
+                 later_action_cache: Optional[bool] = None):
         """`wide_actions` goes to the default search (SampledMCTS: action spaces up to 255 instead of
-        64; None reads `config.wide_actions`); a `make_mcts` of the caller's decides for itself."""
+        64; None reads `config.wide_actions`), and so does `later_action_cache` (the later agents'
+        greedy actions from a per-node cache; None reads `config.later_action_cache`); a `make_mcts` of
+        the caller's decides for itself."""
         self.model, self.config, self.total = model, config, int(total)
         self.rank, self.world = _rank_world(group)
         if rank is not None or world is not None:  # a shard without a process group (single-GPU tests)
@@ -101,7 +105,7 @@ class _Shard:
         # the same generator state on every rank: sharded draws are sliced from whole-batch draws
         self.np_random = np.random.RandomState(seed)
         self.broadcaster, self.src, self.group = broadcaster, src, group
-        self.make_mcts = make_mcts or (lambda c, r, s: _default_mcts(c, r, s, wide_actions))
+        self.make_mcts = make_mcts or (lambda c, r, s: _default_mcts(c, r, s, wide_actions, later_action_cache))
         self.device = device
         self.model_index = -1
         if broadcaster is not None and self.rank == src and broadcaster.model_index < 0:
