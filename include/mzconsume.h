@@ -20,6 +20,10 @@
  * the same rule and are bit-identical to the reference's numpy arithmetic.
  *
  * Exported only by the product library (mazero_amd/_build/libmzmcts.so); device memory only.
+ *
+ * Active roots: in mz_select_actions, mz_eps_greedy and mz_marginal_policy, B below is the handle's
+ * active-root count (mz_set_active_roots, include/mzdriver.h; root_num unless it was set): every
+ * buffer holds B rows, lanes past B write nothing.
  */
 #ifndef MZCONSUME_H
 #define MZCONSUME_H
@@ -46,7 +50,8 @@ extern "C" {
  * probs = v ** (1 / temperature) / sum(...): exact repeated products when 1/temperature is an
  * integer up to 8 (the reference's schedule uses 1, 2, 4; config.py:392-401), else the device pow.
  * A root without children or without visits gets -1 (the reference asserts / draws from the
- * legal actions instead; neither happens after num_simulations >= 1). */
+ * legal actions instead; neither happens after num_simulations >= 1).
+ * B = the handle's active roots (mz_set_active_roots): every buffer holds B rows. */
 int mz_select_actions(mz_batch *b, const int32_t *degrees, const int32_t *visits, const int32_t *actions,
                       int width, double temperature, int deterministic, const double *uniforms, int32_t *pos_out,
                       int32_t *action_out, double *entropy_out);
@@ -57,13 +62,15 @@ int mz_select_actions(mz_batch *b, const int32_t *degrees, const int32_t *visits
  * categorical(w; u) = the first a with cumsum(w)[a] / sum(w) > u (float64), i.e. a draw from
  * torch.distributions.Categorical(w).  u_eps float32 [B], u_cat float64 [B] in [0, 1): the
  * reference draws them from torch's global generator per root; the caller supplies them (the same
- * distribution, not the same stream).  A root with no legal action keeps its greedy action. */
+ * distribution, not the same stream).  A root with no legal action keeps its greedy action.
+ * B = the handle's active roots (mz_set_active_roots): every buffer holds B rows. */
 int mz_eps_greedy(mz_batch *b, const int32_t *legal, int64_t legal_stride, float eps, const float *u_eps,
                   const double *u_cat, int32_t *action_io);
 
 enum mz_marginal_mode {
     MZ_MARGINAL_GIVEN = 0,  /* self-play record: action given (core/selfplay_worker.py:278-290) */
     MZ_MARGINAL_ARGMAX = 1, /* reanalyze: action = argmax(marginal * legal) (reanalyze_worker.py:303-319) */
+    MZ_MARGINAL_ARGMAX_LEGAL = 2, /* full-game reanalysis: the action alone (reanalyze_worker.py:563-570) */
 };
 
 /* One agent's marginal visit distribution dist = marginal / sum(marginal) (float64) at each root:
@@ -74,7 +81,13 @@ enum mz_marginal_mode {
  * entropy 0 (as the self-play worker); ARGMAX writes action -1 and leaves prob_io and entropy_out
  * unchanged -- the reference draws that root's action from np_random -- for the caller to resolve.
  * marginal: int32 [B, A] (row stride marginal_stride); legal: int32 [B, A] (row stride
- * legal_stride), required for ARGMAX, ignored by GIVEN. */
+ * legal_stride), required for ARGMAX, ignored by GIVEN.
+ *   MZ_MARGINAL_ARGMAX_LEGAL (make_renalyze_update, reanalyze_worker.py:563-570): when the int64 sum
+ *   over a of marginal[i, a] * legal[i, a] is > 0, action_io[i] = the first argmax of those products;
+ *   otherwise action_io[i] = -1 (no visit on a legal action: the reference draws the action from
+ *   np_random, the caller resolves it).  Neither prob_io nor entropy_out is touched; both may be NULL.
+ *   legal is required.
+ * B = the handle's active roots (mz_set_active_roots): every buffer holds B rows. */
 int mz_marginal_policy(mz_batch *b, const int32_t *marginal, int64_t marginal_stride, const int32_t *legal,
                        int64_t legal_stride, int mode, int32_t *action_io, double *prob_io, double *entropy_out);
 

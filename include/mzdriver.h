@@ -40,6 +40,23 @@ enum mz_dtype { MZ_DT_F32 = 0, MZ_DT_F16 = 1 };
  * keep one device arena across searches. */
 int mz_reseed(mz_batch *b, uint32_t random_seed);
 
+/* Active roots: a handle of root_num trees serving a search of n <= root_num roots (a driver of fixed
+ * capacity pads the inputs of the other trees, mazero_amd.mcts_sampled root_capacity).  After
+ * mz_set_active_roots(b, n), "every root" means roots [0, n) in
+ *   - the host and device getters: mz_get_roots_values, mz_get_roots_marginal_visit_count,
+ *     mz_get_roots_marginal_priors, mz_get_roots_sampled_padded and mz_get_roots_device write n rows;
+ *   - mz_get_root_sampled / mz_get_num_children_of_root: tree_id < n, else MZ_ERR_ARG;
+ *   - the consumers of include/mzconsume.h that take their row count from the handle:
+ *     mz_select_actions, mz_eps_greedy, mz_marginal_policy launch lanes for n rows.
+ * In those calls the caller's buffers hold n rows.  The search, prepare and glue entry points
+ * (mz_prepare*, mz_select, mz_expand_backup*, mz_gather_rows, the mz_*_glue* and mz_joint_action* calls,
+ * mz_expand_backup_readback with caller buffers) still run all root_num trees and read root_num input
+ * rows.  The packed readback keeps its layout for root_num roots; rows [0, n) of each section are a
+ * prefix of it.  1 <= n <= root_num, else MZ_ERR_ARG.  Host-side state only: nothing is launched and a
+ * packed readback that is ready stays ready.  A new handle has n = root_num; mz_reseed leaves n alone. */
+int mz_set_active_roots(mz_batch *b, int n);
+int mz_get_active_roots(mz_batch *b, int *n);
+
 /* Tell the handle that its trees were changed by work it did not enqueue itself -- the replay of
  * a captured graph of mz_* calls -- so that host-side readback caches are dropped.  (Captured
  * launches read the seed and every input from device memory, so a replay after mz_reseed and

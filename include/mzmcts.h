@@ -191,6 +191,8 @@ int mz_gather_rows(mz_batch *b, const void *pool, int64_t pool_slot_stride, int6
                    const int32_t *idx_x, void *out);
 
 /* --- readbacks ------------------------------------------------------------------------- */
+/* On the product library B below is the handle's active-root count (mz_set_active_roots,
+ * include/mzdriver.h; root_num unless it was set): the getters write rows [0, B) and tree_id < B. */
 /* CTree_batch::get_roots_values (cnode.cpp:672-679): out [B]. */
 int mz_get_roots_values(mz_batch *b, float *out, int mem);
 /* CTree_batch::get_roots_marginal_visit_count (cnode.cpp:682-690): out [B, agent_num, A]. */

@@ -112,6 +112,8 @@ MZ_INV_LOGITS, MZ_INV_PROBS, MZ_INV_EXPECTATION = 0, 1, 2  # enum mz_inv_stage
 DRIVER_SIGNATURES = {
     "mz_reseed": (_i, [_p, C.c_uint32]),
     "mz_state_changed": (_i, [_p]),
+    "mz_set_active_roots": (_i, [_p, _i]),
+    "mz_get_active_roots": (_i, [_p, C.POINTER(_i)]),
     "mz_policy_glue": (_i, [_p, _p, _i, _i64, _i64, C.c_double, _p, _p]),
     "mz_root_glue": (_i, [_p, _p, _i, _i64, _i64, _p, _i64, _p, C.c_double, C.c_double, _p, _p, _p]),
     "mz_joint_action": (_i, [_p, _p, _i, _i, _i, _p, _i, _p, _p]),
@@ -143,7 +145,7 @@ DRIVER_SIGNATURES = {
 DRIVER_EXPORTS = sorted(DRIVER_SIGNATURES)
 
 # include/mzconsume.h (on-device consumers of the search output; product library only)
-MZ_MARGINAL_GIVEN, MZ_MARGINAL_ARGMAX = 0, 1
+MZ_MARGINAL_GIVEN, MZ_MARGINAL_ARGMAX, MZ_MARGINAL_ARGMAX_LEGAL = 0, 1, 2  # enum mz_marginal_mode
 CONSUME_SIGNATURES = {
     "mz_select_actions": (_i, [_p, _p, _p, _p, _i, C.c_double, _i, _p, _p, _p, _p]),
     "mz_eps_greedy": (_i, [_p, _p, _i64, _f, _p, _p, _p]),

@@ -6,7 +6,10 @@ decide per root in Python:
   counts with `np_random` (core/utils.py:289-316), `eps_greedy_action` with torch's generator
   (core/utils.py:319-334), then the stored policy probability and visit entropy;
 - reanalyze (core/reanalyze_worker.py:275-366, `_prepare_policy_re`): the action
-  argmax(marginal visits * legal), and the product of the agents' marginal visit distributions.
+  argmax(marginal visits * legal), and the product of the agents' marginal visit distributions;
+- full-game reanalysis (core/reanalyze_worker.py:491-611, `make_renalyze_update`): the same per agent
+  turn over the len(game) steps of one game, with the reference's np_random fallback for a root whose
+  visits all lie on illegal actions (`reanalyze_game`, `write_game`).
 
 Here the same decisions are made on the device from `DeviceSearchOutput`, in the tree handle's
 stream; the next agent's search takes the actions as a device tensor, so an environment step
@@ -21,13 +24,15 @@ not the same stream), or caller-supplied ones.
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
 from typing import List, NamedTuple, Optional, Tuple
 
 import numpy as np
 import torch
 
-from ._capi import MZ_MARGINAL_ARGMAX, MZ_MARGINAL_GIVEN, MZ_VALUE_NON_RE, MZ_VALUE_RE, check
+from ._capi import (MZ_MARGINAL_ARGMAX, MZ_MARGINAL_ARGMAX_LEGAL, MZ_MARGINAL_GIVEN, MZ_VALUE_NON_RE, MZ_VALUE_RE,
+                    check)
 from .mcts_sampled import DeviceSearchOutput
 
 
@@ -57,6 +62,13 @@ def _tree(out: DeviceSearchOutput):
     if out.tree is None:
         raise ValueError("DeviceSearchOutput without its tree handle (use SampledMCTS.batch_search_device)")
     tb = out.tree
+    # the consumers launch one lane per active root of the handle: `out` must be the handle's current
+    # search (on a root_capacity driver a later search of another root count changes the active count)
+    ref = out.degrees if out.degrees is not None else out.marginal_visit_count
+    if ref is not None and ref.shape[0] != tb.active_roots:
+        raise ValueError(f"this search output holds {ref.shape[0]} roots but its tree handle now has "
+                         f"{tb.active_roots} active roots: consume an output before a search of another root "
+                         "count runs on the same handle")
     tb._sync_stream()
     return tb
 
@@ -93,8 +105,11 @@ def eps_greedy(out: DeviceSearchOutput, action: torch.Tensor, legal: torch.Tenso
     if legal.stride(-1) != 1:
         legal = legal.contiguous()
     lib = tb._lib
-    check(lib, lib.mz_eps_greedy(tb._h, _p(legal), int(legal.stride(0)), float(eps), _p(u_eps.contiguous()),
-                                 _p(u_cat.contiguous()), _p(action)), "eps_greedy")
+    # (named, so that a contiguous copy of a strided row lives until the launch is enqueued: as unnamed
+    # temporaries the two copies were freed at once and could share one block of torch's allocator)
+    u_eps, u_cat = u_eps.contiguous(), u_cat.contiguous()
+    check(lib, lib.mz_eps_greedy(tb._h, _p(legal), int(legal.stride(0)), float(eps), _p(u_eps), _p(u_cat),
+                                 _p(action)), "eps_greedy")
     return action
 
 
@@ -102,7 +117,8 @@ def marginal_policy(out: DeviceSearchOutput, mode: int, action: torch.Tensor, pr
                     legal: Optional[torch.Tensor] = None, entropy: Optional[torch.Tensor] = None):
     """One agent's marginal visit distribution at each root (include/mzconsume.h
     mz_marginal_policy): ARGMAX picks `action`, both modes multiply `prob` (float64 [B]) by the
-    distribution at the action and write the visit entropy."""
+    distribution at the action and write the visit entropy.  ARGMAX_LEGAL writes `action` only (-1
+    where no visit lies on a legal action); `prob` and `entropy` may be None."""
     tb = _tree(out)
     marginal = out.marginal_visit_count[:, 0, :]
     if marginal.stride(-1) != 1:
@@ -258,6 +274,93 @@ def reanalyze_policy_targets(mcts, model, network_output, legal_actions_lst, pol
         pv = pv.reshape(B, 1)
     return ReanalyzePolicy(current.reshape(B, 1, N), prob.to(torch.float32).reshape(B, 1),
                            torch.ones(B, 1, dtype=torch.float32, device=dev), masks, value0, value0, pv)
+
+
+class GameReanalysis(NamedTuple):
+    """What make_renalyze_update computes for the T = len(game) steps of one game
+    (reanalyze_worker.py:515-596, :604-607), as device tensors."""
+
+    actions: torch.Tensor       # int32 [T, N]: the chosen joint actions
+    policy_probs: torch.Tensor  # float32 [T, 1]: the probability of the chosen joint action
+    root_values: torch.Tensor   # float32 [T, 1]: agent 0's search value
+    pred_values: Optional[torch.Tensor]  # network_output.value, [T, 1] or [T] as given (None: another shape)
+
+
+def _device_ctx(dev):
+    return torch.cuda.device(dev) if torch.device(dev).type == "cuda" else contextlib.nullcontext()
+
+
+def reanalyze_game(mcts, model, network_output, legal_actions_lst, device=None) -> GameReanalysis:
+    """`make_renalyze_update` after its initial inference (reanalyze_worker.py:507-596) for the T steps
+    of one game: per agent turn a search of the T roots (add_noise=True, sampled_tau=1.0) conditioned on
+    the earlier agents' chosen actions on the device, then the action argmax(marginal visits * legal)
+    (MZ_MARGINAL_ARGMAX_LEGAL).  A root whose visits all lie on illegal actions comes back -1 and is
+    resolved on the host as the reference does (:568-570), in root order and before the next agent's
+    search: `np_random.choice(np.where(legal_row == 1)[0])`, or 0 when no action is legal; this is the
+    one small device-to-host read of the action column per agent.  After the last agent the probability
+    of the chosen joint action is the running float64 product of the agents' marginal visit
+    distributions at their actions (:587-596), stored as float32.  Requires num_simulations >= 1.
+
+    On a `SampledMCTS(root_capacity >= max_moves)` games of every length share one set of recorded
+    loops."""
+    if mcts.config.num_simulations < 1:
+        raise ValueError("reanalyze_game needs num_simulations >= 1")
+    hidden = network_output.hidden_state
+    dev = hidden.device
+    T = hidden.shape[0]
+    legal_np = legal_actions_lst.cpu().numpy() if isinstance(legal_actions_lst, torch.Tensor) \
+        else np.asarray(legal_actions_lst)
+    N = legal_np.shape[1]
+    legal = _dev_i32(legal_np, dev)
+    current = torch.zeros(T, N, dtype=torch.int32, device=dev)
+    outs, value0 = [], None
+    for k in range(N):
+        factor = current[:, :k] if k > 0 else None
+        out = mcts.batch_search_device(model, network_output, k, factor, N, legal_np, device, add_noise=True,
+                                       sampled_tau=1.0)
+        outs.append(out)
+        if k == 0:
+            value0 = out.value.reshape(T, 1)
+        a = torch.empty(T, dtype=torch.int32, device=dev)
+        with _device_ctx(dev):
+            marginal_policy(out, MZ_MARGINAL_ARGMAX_LEGAL, a, None, legal=legal[:, k, :])
+        a_host = a.cpu().numpy()
+        missing = np.flatnonzero(a_host < 0)
+        if missing.size:  # :568-570, in root order
+            a_host = a_host.copy()
+            for i in missing:
+                options = np.flatnonzero(legal_np[i, k, :] == 1)
+                a_host[i] = mcts.np_random.choice(options) if options.size else 0
+            a.copy_(torch.from_numpy(a_host))
+        current[:, k] = a
+    prob = torch.ones(T, dtype=torch.float64, device=dev)
+    with _device_ctx(dev):
+        for k in range(N):  # :587-596, agent order
+            marginal_policy(outs[k], MZ_MARGINAL_GIVEN, current[:, k].contiguous(), prob)
+    pv = torch.as_tensor(network_output.value).to(dev)
+    if not ((pv.ndim == 2 and pv.shape[1] == 1) or pv.ndim == 1):
+        pv = None  # (the reference leaves game.pred_values as they are, :608-609)
+    return GameReanalysis(current, prob.to(torch.float32).reshape(T, 1), value0, pv)
+
+
+def write_game(game, result: GameReanalysis, model_index: int):
+    """Store a `reanalyze_game` result on `game` (any object with these attributes) in the per-step list
+    form the reference's replay code reads (reanalyze_worker.py:598-607): one entry per step, each a view
+    of the result's row.  Returns `game`."""
+    actions = result.actions.cpu().numpy()
+    T, N = actions.shape
+    probs = result.policy_probs.cpu().numpy().reshape(T, 1)
+    values = result.root_values.cpu().numpy().reshape(T, 1)
+    game.model_indices = np.full(T, model_index)
+    game.sampled_actions = list(actions.reshape(T, 1, N))       # [1, N] each
+    game.sampled_policies = list(probs)                         # [1] each
+    game.sampled_padding_masks = list(np.ones((T, 1), np.bool_))
+    game.sampled_qvalues = list(values)
+    game.root_values = list(values[:, 0])                       # scalars
+    if result.pred_values is not None:
+        pred = result.pred_values.cpu().numpy()
+        game.pred_values = list(pred[:, 0]) if pred.ndim == 2 else pred.tolist()
+    return game
 
 
 # ------------------------------------------------------------------------------------------------

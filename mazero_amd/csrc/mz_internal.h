@@ -16,4 +16,6 @@ MZ_HIDDEN int mz_internal_launch_info(mz_batch *b, int *B, int *A, hipStream_t *
 MZ_HIDDEN void mz_internal_enqueued(mz_batch *b);
 // agent_num of the handle (0 for a null handle).
 MZ_HIDDEN int mz_internal_agent_num(mz_batch *b);
+// the handle's active roots (include/mzdriver.h mz_set_active_roots; 0 for a null handle).
+MZ_HIDDEN int mz_internal_active_roots(mz_batch *b);
 }  // extern "C"

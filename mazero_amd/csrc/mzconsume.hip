@@ -158,6 +158,26 @@ __global__ __launch_bounds__(kLanes) void k_marginal_policy(int B, int A, const 
     }
 }
 
+// MZ_MARGINAL_ARGMAX_LEGAL: the action of one agent turn of the full-game reanalysis
+// (reanalyze_worker.py:563-570).  Writes action_io only.
+__global__ __launch_bounds__(kLanes) void k_marginal_argmax_legal(int B, int A, const int *__restrict__ marginal,
+                                                                  long long mstride, const int *__restrict__ legal,
+                                                                  long long lstride, int *action_io) {
+    const int i = blockIdx.x * kLanes + threadIdx.x;
+    if (i >= B) return;
+    const int *m = marginal + (long long)i * mstride;
+    const int *l = legal + (long long)i * lstride;
+    // masked_visits = marginal_visits * legal_actions; np.sum(masked_visits) > 0, else the host draws
+    int best = 0;
+    long long bv = (long long)m[0] * l[0], sum = bv;
+    for (int a = 1; a < A; ++a) {
+        const long long v = (long long)m[a] * l[a];
+        sum += v;
+        if (v > bv) bv = v, best = a;  // np.argmax: first maximum
+    }
+    action_io[i] = sum > 0 ? best : -1;
+}
+
 // ---- reanalyze batch targets (reanalyze_worker.py:376-489) -----------------------------------
 
 // One row of _prepare_reward_value_re (:137-157) / _prepare_reward_value_non_re (:186-204).  The
@@ -401,6 +421,15 @@ int device_plan(int n, hipStream_t stream, DevicePlan *out) {
     return MZ_OK;
 }
 
+// mz_internal_launch_info with the handle's active roots for B: the consumers' buffers hold rows
+// [0, active) (include/mzdriver.h mz_set_active_roots)
+int consumer_info(mz_batch *b, int *B, int *A, hipStream_t *stream) {
+    int rc = mz_internal_launch_info(b, B, A, stream);
+    if (rc) return rc;
+    *B = mz_internal_active_roots(b);
+    return MZ_OK;
+}
+
 // the stream of the handle (b != NULL) or the caller's (include/mzconsume.h)
 int target_stream(mz_batch *b, void *stream, hipStream_t *out) {
     if (!b) {
@@ -426,7 +455,7 @@ int mz_select_actions(mz_batch *b, const int32_t *degrees, const int32_t *visits
                       int32_t *action_out, double *entropy_out) {
     int B = 0, A = 0;
     hipStream_t stream = nullptr;
-    int rc = mz_internal_launch_info(b, &B, &A, &stream);
+    int rc = consumer_info(b, &B, &A, &stream);
     if (rc) return rc;
     if (!degrees || !visits || !actions || !pos_out || !action_out || (!deterministic && !uniforms))
         return mz_internal_fail(MZ_ERR_ARG, "mz_select_actions: null buffer");
@@ -445,7 +474,7 @@ int mz_eps_greedy(mz_batch *b, const int32_t *legal, int64_t legal_stride, float
                   const double *u_cat, int32_t *action_io) {
     int B = 0, A = 0;
     hipStream_t stream = nullptr;
-    int rc = mz_internal_launch_info(b, &B, &A, &stream);
+    int rc = consumer_info(b, &B, &A, &stream);
     if (rc) return rc;
     if (!legal || !u_eps || !u_cat || !action_io) return mz_internal_fail(MZ_ERR_ARG, "mz_eps_greedy: null buffer");
     if (legal_stride < A) return mz_internal_fail(MZ_ERR_ARG, "mz_eps_greedy: legal rows hold fewer than A entries");
@@ -459,8 +488,18 @@ int mz_marginal_policy(mz_batch *b, const int32_t *marginal, int64_t marginal_st
                        int64_t legal_stride, int mode, int32_t *action_io, double *prob_io, double *entropy_out) {
     int B = 0, A = 0;
     hipStream_t stream = nullptr;
-    int rc = mz_internal_launch_info(b, &B, &A, &stream);
+    int rc = consumer_info(b, &B, &A, &stream);
     if (rc) return rc;
+    if (mode == MZ_MARGINAL_ARGMAX_LEGAL) {  // action_io only: prob_io and entropy_out may be NULL
+        if (!marginal || !legal || !action_io) return mz_internal_fail(MZ_ERR_ARG, "mz_marginal_policy: null buffer");
+        if (marginal_stride < A || legal_stride < A)
+            return mz_internal_fail(MZ_ERR_ARG, "mz_marginal_policy: rows hold fewer than A entries");
+        hipLaunchKernelGGL(k_marginal_argmax_legal, dim3((B + kLanes - 1) / kLanes), dim3(kLanes), 0, stream, B, A,
+                           (const int *)marginal, (long long)marginal_stride, (const int *)legal,
+                           (long long)legal_stride, (int *)action_io);
+        mz_internal_enqueued(b);
+        return launch_status();
+    }
     if (mode != MZ_MARGINAL_GIVEN && mode != MZ_MARGINAL_ARGMAX)
         return mz_internal_fail(MZ_ERR_ARG, "mz_marginal_policy: bad mode");
     if (!marginal || !action_io || !prob_io || (mode == MZ_MARGINAL_ARGMAX && !legal))

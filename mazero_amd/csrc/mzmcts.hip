@@ -6556,6 +6556,7 @@ __global__ __launch_bounds__(64) void k_readback(const Params *__restrict__ prm,
 struct mz_batch {
     int B, N, A, K, S, P, E, W, PS, Wd;
     int NA;  // N * A: per-root policy / marginal entries
+    int active = 0;  // roots [0, active) are what the getters and consumers see (mz_set_active_roots)
     int device;
     Geo geo;
     Dev dev;
@@ -7398,6 +7399,7 @@ int mz_create(int B, int N, int A, int K, int S, float delta_lb, uint32_t seed, 
         return fail(MZ_ERR_UNSUPPORTED, "root_num * (1 + min(K, A^N) * (simulation_num + 1)) >= 2^32 nodes");
     auto *b = new mz_batch;
     b->B = B;
+    b->active = B;
     b->N = N;
     b->A = A;
     b->NA = N * A;
@@ -7987,6 +7989,19 @@ int mz_reseed(mz_batch *b, uint32_t seed) {
     return MZ_OK;
 }
 
+int mz_set_active_roots(mz_batch *b, int n) {
+    if (!b) return fail(MZ_ERR_ARG, "null handle");
+    if (n < 1 || n > b->B) return fail(MZ_ERR_ARG, "active roots must be in [1, root_num]");
+    b->active = n;  // host state only: the packed readback keeps its layout and stays valid
+    return MZ_OK;
+}
+
+int mz_get_active_roots(mz_batch *b, int *n) {
+    if (!b || !n) return fail(MZ_ERR_ARG, "mz_get_active_roots: null argument");
+    *n = b->active;
+    return MZ_OK;
+}
+
 int mz_state_changed(mz_batch *b) {
     if (!b) return fail(MZ_ERR_ARG, "null handle");
     OrderMark om{b};
@@ -8046,6 +8061,8 @@ int mz_internal_launch_info(mz_batch *b, int *B, int *A, hipStream_t *stream) {
 
 int mz_internal_agent_num(mz_batch *b) { return b ? b->N : 0; }
 
+int mz_internal_active_roots(mz_batch *b) { return b ? b->active : 0; }
+
 void mz_internal_enqueued(mz_batch *b) {
     if (!b) return;
     b->dirty = true;
@@ -8082,7 +8099,8 @@ int mz_get_roots_device(mz_batch *b, float discount, const mz_readback_out *out)
     o.deg = out->degrees;
     for (int f = 0; f < MZ_F_COUNT; ++f) o.f[f] = (int *)out->sampled[f];
     b->dirty = true;
-    hipLaunchKernelGGL(k_readback, dim3(b->B), dim3(kWave), 0, b->stream, b->prm, discount, b->Wd, o);
+    // one workgroup per root: the caller's buffers hold rows [0, active) (mz_set_active_roots)
+    hipLaunchKernelGGL(k_readback, dim3(b->active), dim3(kWave), 0, b->stream, b->prm, discount, b->Wd, o);
     HIP_TRY(hipGetLastError());
     return MZ_OK;
 }
@@ -8155,13 +8173,13 @@ int mz_get_roots_values(mz_batch *b, float *out, int mem) {
     if (mem == MZ_MEM_DEVICE) {
         rc = readback_dev(b, b->rb_dev_valid ? b->rb_disc : 0.f);
         if (rc) return rc;
-        rc = copy_words(b, out, b->rb_dev, (size_t)b->B);
+        rc = copy_words(b, out, b->rb_dev, (size_t)b->active);
         if (rc) return rc;
         return MZ_OK;
     }
     rc = readback(b, (b->rb_valid || b->rb_dev_valid) ? b->rb_disc : 0.f);
     if (rc) return rc;
-    std::memcpy(out, b->rb_host, 4 * (size_t)b->B);
+    std::memcpy(out, b->rb_host, 4 * (size_t)b->active);
     return MZ_OK;
 }
 
@@ -8173,7 +8191,7 @@ int mz_get_roots_marginal_visit_count(mz_batch *b, int32_t *out, int mem) {
     rc = (mem == MZ_MEM_DEVICE) ? readback_dev(b, b->rb_dev_valid ? b->rb_disc : 0.f)
                                 : readback(b, (b->rb_valid || b->rb_dev_valid) ? b->rb_disc : 0.f);
     if (rc) return rc;
-    const size_t n = (size_t)b->B * b->NA;
+    const size_t n = (size_t)b->active * b->NA;  // rows [0, active) of the section
     if (mem == MZ_MEM_DEVICE) {
         rc = copy_words(b, out, b->rb_dev + b->B, n);
         if (rc) return rc;
@@ -8191,19 +8209,19 @@ int mz_get_roots_marginal_priors(mz_batch *b, float *out, int mem) {
     rc = (mem == MZ_MEM_DEVICE) ? readback_dev(b, b->rb_dev_valid ? b->rb_disc : 0.f)
                                 : readback(b, (b->rb_valid || b->rb_dev_valid) ? b->rb_disc : 0.f);
     if (rc) return rc;
-    const size_t n = (size_t)b->B * b->NA;
+    const size_t sec = (size_t)b->B * b->NA, n = (size_t)b->active * b->NA;
     if (mem == MZ_MEM_DEVICE) {
-        rc = copy_words(b, out, b->rb_dev + b->B + n, n);
+        rc = copy_words(b, out, b->rb_dev + b->B + sec, n);
         if (rc) return rc;
         return MZ_OK;
     }
-    std::memcpy(out, b->rb_host + b->B + n, 4 * n);
+    std::memcpy(out, b->rb_host + b->B + sec, 4 * n);
     return MZ_OK;
 }
 
 int mz_get_num_children_of_root(mz_batch *b, int tree_id, int32_t *out) {
     if (!b) return fail(MZ_ERR_ARG, "null handle");
-    if (tree_id < 0 || tree_id >= b->B) return fail(MZ_ERR_ARG, "tree_id out of range");
+    if (tree_id < 0 || tree_id >= b->active) return fail(MZ_ERR_ARG, "tree_id out of range");
     int rc = ensure_device(b);
     if (rc) return rc;
     rc = readback(b, (b->rb_valid || b->rb_dev_valid) ? b->rb_disc : 0.f);
@@ -8220,7 +8238,7 @@ int mz_max_children(mz_batch *b, int32_t *out) {
 
 int mz_get_root_sampled(mz_batch *b, int field, int tree_id, float discount, void *out) {
     if (!b) return fail(MZ_ERR_ARG, "null handle");
-    if (tree_id < 0 || tree_id >= b->B) return fail(MZ_ERR_ARG, "tree_id out of range");
+    if (tree_id < 0 || tree_id >= b->active) return fail(MZ_ERR_ARG, "tree_id out of range");
     if (field < 0 || field >= MZ_F_COUNT) return fail(MZ_ERR_ARG, "unknown field");
     int rc = ensure_device(b);
     if (rc) return rc;
@@ -8241,19 +8259,19 @@ int mz_get_roots_sampled_padded(mz_batch *b, int field, float discount, void *ou
     const float disc = field == MZ_F_QVALUES ? discount : ((b->rb_valid || b->rb_dev_valid) ? b->rb_disc : discount);
     rc = (mem == MZ_MEM_DEVICE) ? readback_dev(b, disc) : readback(b, disc);
     if (rc) return rc;
-    const size_t n = (size_t)b->B * rb_field_width(b, field);
+    const size_t n = (size_t)b->active * rb_field_width(b, field);
     const size_t dego = rb_deg_base(b);
     if (mem == MZ_MEM_DEVICE) {
         rc = copy_words(b, out, b->rb_dev + rb_field_base(b, field), n);
         if (rc) return rc;
         if (degrees) {
-            rc = copy_words(b, degrees, b->rb_dev + dego, (size_t)b->B);
+            rc = copy_words(b, degrees, b->rb_dev + dego, (size_t)b->active);
             if (rc) return rc;
         }
         return MZ_OK;
     }
     std::memcpy(out, b->rb_host + rb_field_base(b, field), 4 * n);
-    if (degrees) std::memcpy(degrees, b->rb_host + dego, 4 * (size_t)b->B);
+    if (degrees) std::memcpy(degrees, b->rb_host + dego, 4 * (size_t)b->active);
     return MZ_OK;
 }
 

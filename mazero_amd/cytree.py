@@ -128,6 +128,8 @@ class Tree_batch:
         # the device the handle's arena lives on (mz_create allocates on the current device)
         self.device_index = torch.cuda.current_device() if self._on_device else None
         self._maxdeg = None
+        # mz_get_active_roots where the library has it (include/mzdriver.h, product library only)
+        self._get_active = getattr(lib, "mz_get_active_roots", None)
 
     # -- lifetime ---------------------------------------------------------------------------
     def __del__(self):
@@ -265,6 +267,27 @@ class Tree_batch:
         self._sync_stream()
         check(self._lib, self._lib.mz_reseed(self._h, int(random_seed) & 0xFFFFFFFF), "reseed")
 
+    def set_active_roots(self, n: int):
+        """From now on the getters and the on-device consumers see roots [0, n) only: their outputs and
+        per-root lists hold n rows (include/mzdriver.h mz_set_active_roots; product library only).  The
+        search still runs all root_num trees.  Launches nothing."""
+        fn = getattr(self._lib, "mz_set_active_roots", None)
+        if fn is None:
+            raise RuntimeError("set_active_roots: this tree library has no mz_set_active_roots "
+                               "(include/mzdriver.h, product library only)")
+        check(self._lib, fn(self._h, int(n)), "set_active_roots")
+
+    @property
+    def active_roots(self) -> int:
+        """The handle's active-root count, read from the library (a host-side call; root_num unless
+        set_active_roots changed it, and always root_num on a library without the entry point).  The
+        getters size their outputs by it."""
+        if self._get_active is None:
+            return self.root_num
+        n = C.c_int(0)
+        check(self._lib, self._get_active(self._h, C.byref(n)), "active_roots")
+        return int(n.value)
+
     def state_changed(self):
         """Drop host-side readback caches after replaying a captured graph of this handle's calls."""
         self._sync_stream()
@@ -273,7 +296,7 @@ class Tree_batch:
     # -- device readbacks (no host synchronisation) -------------------------------------------
     def get_roots_values_device(self, out=None):
         dev = torch.device("cuda", self.device_index)  # (the arena's device)
-        out = torch.empty(self.root_num, dtype=torch.float32, device=dev) if out is None else out
+        out = torch.empty(self.active_roots, dtype=torch.float32, device=dev) if out is None else out
         self._sync_stream()
         check(self._lib, self._lib.mz_get_roots_values(self._h, C.c_void_p(out.data_ptr()), MZ_MEM_DEVICE),
               "get_roots_values_device")
@@ -282,7 +305,7 @@ class Tree_batch:
     def get_roots_marginal_device(self, visit_out=None, prior_out=None):
         """(marginal visit counts int32 [B, N, A], marginal priors f32 [B, N, A]) on the device."""
         dev = torch.device("cuda", self.device_index)  # (the arena's device)
-        shape = (self.root_num, self.agent_num, self.action_space_size)
+        shape = (self.active_roots, self.agent_num, self.action_space_size)
         visit_out = torch.empty(shape, dtype=torch.int32, device=dev) if visit_out is None else visit_out
         prior_out = torch.empty(shape, dtype=torch.float32, device=dev) if prior_out is None else prior_out
         self._sync_stream()
@@ -292,9 +315,11 @@ class Tree_batch:
                                                                  MZ_MEM_DEVICE), "marginal_priors_device")
         return visit_out, prior_out
 
-    def _readback_out(self, values, marginal_visit_count, marginal_priors, degrees, sampled, what):
-        """The mz_readback_out list of caller-provided device tensors (checked: see _check_out)."""
-        B, NA = self.root_num, self.agent_num * self.action_space_size
+    def _readback_out(self, values, marginal_visit_count, marginal_priors, degrees, sampled, what, rows):
+        """The mz_readback_out list of caller-provided device tensors (checked: see _check_out).  `rows`:
+        the rows the launch writes: the active roots for mz_get_roots_device, all root_num for
+        mz_expand_backup_readback (include/mzdriver.h)."""
+        B, NA = int(rows), self.agent_num * self.action_space_size
         W = self.max_children() if sampled else 0
         dv = self.device_index
         _check_out(values, B, torch.float32, "values", dv)
@@ -318,7 +343,8 @@ class Tree_batch:
         """Every requested readback of all roots in ONE launch, written into the given device tensors
         (include/mzmcts.h mz_get_roots_device): values [B] f32, marginal_* [B, N, A], degrees [B] int32,
         sampled {field name: [B, max_children(*N)]} as get_roots_sampled_padded_device lays them out."""
-        o = self._readback_out(values, marginal_visit_count, marginal_priors, degrees, sampled, "get_roots_device")
+        o = self._readback_out(values, marginal_visit_count, marginal_priors, degrees, sampled, "get_roots_device",
+                               self.active_roots)
         self._sync_stream()
         check(self._lib, self._lib.mz_get_roots_device(self._h, float(discount), C.byref(o)), "get_roots_device")
 
@@ -332,7 +358,8 @@ class Tree_batch:
         o = None
         if out is not None:
             o = self._readback_out(out.get("values"), out.get("marginal_visit_count"), out.get("marginal_priors"),
-                                   out.get("degrees"), out.get("sampled"), "expansion_backup_readback_device")
+                                   out.get("degrees"), out.get("sampled"), "expansion_backup_readback_device",
+                                   self.root_num)  # (this launch writes every tree's row)
         self._sync_stream()
         rc = self._lib.mz_expand_backup_readback(
             self._h, int(hidden_state_index_x), float(discount), int(sampled_times),
@@ -347,7 +374,7 @@ class Tree_batch:
 
     def get_roots_sampled_padded_device(self, name: str, discount: float = 0.0, degrees_out=None):
         """Device form of get_roots_sampled_padded: (tensor [B, maxdeg(*N)], degrees int32 [B])."""
-        B, N = self.root_num, self.agent_num
+        B, N = self.active_roots, self.agent_num
         W = self.max_children()
         dev = torch.device("cuda", self.device_index)  # (the arena's device)
         width = W * N if name == "actions" else W
@@ -363,24 +390,26 @@ class Tree_batch:
     # -- readbacks (cytree.pyx:93-241) ----------------------------------------------------------
     def get_roots_values(self):
         self._sync_stream()
-        out = np.empty(self.root_num, np.float32)
+        out = np.empty(self.active_roots, np.float32)
         check(self._lib, self._lib.mz_get_roots_values(self._h, out.ctypes.data_as(C.c_void_p), MZ_MEM_HOST),
               "get_roots_values")
         return out
 
     def get_roots_marginal_visit_count(self):
         self._sync_stream()
-        out = np.empty(self.root_num * self.agent_num * self.action_space_size, np.int32)
+        rows = self.active_roots
+        out = np.empty(rows * self.agent_num * self.action_space_size, np.int32)
         check(self._lib, self._lib.mz_get_roots_marginal_visit_count(self._h, out.ctypes.data_as(C.c_void_p),
                                                                       MZ_MEM_HOST), "get_roots_marginal_visit_count")
-        return out.reshape(self.root_num, self.agent_num, self.action_space_size)
+        return out.reshape(rows, self.agent_num, self.action_space_size)
 
     def get_roots_marginal_priors(self):
         self._sync_stream()
-        out = np.empty(self.root_num * self.agent_num * self.action_space_size, np.float32)
+        rows = self.active_roots
+        out = np.empty(rows * self.agent_num * self.action_space_size, np.float32)
         check(self._lib, self._lib.mz_get_roots_marginal_priors(self._h, out.ctypes.data_as(C.c_void_p),
                                                                  MZ_MEM_HOST), "get_roots_marginal_priors")
-        return out.reshape(self.root_num, self.agent_num, self.action_space_size)
+        return out.reshape(rows, self.agent_num, self.action_space_size)
 
     def max_children(self) -> int:
         if self._maxdeg is None:
@@ -391,7 +420,7 @@ class Tree_batch:
 
     def get_roots_sampled_padded(self, name: str, discount: float = 0.0):
         """One batched readback: (array [B, maxdeg(, N)], degrees [B])."""
-        B, N = self.root_num, self.agent_num
+        B, N = self.active_roots, self.agent_num
         W = self.max_children()
         dt = np.int32 if name in INT_FIELDS else np.float32
         width = W * N if name == "actions" else W
@@ -409,8 +438,8 @@ class Tree_batch:
         arr, deg = self.get_roots_sampled_padded(name, discount)
         if name == "actions":
             N = self.agent_num
-            return [np.ascontiguousarray(arr[i, : deg[i] * N]).reshape(deg[i], N) for i in range(self.root_num)]
-        return [np.ascontiguousarray(arr[i, : deg[i]]) for i in range(self.root_num)]
+            return [np.ascontiguousarray(arr[i, : deg[i] * N]).reshape(deg[i], N) for i in range(arr.shape[0])]
+        return [np.ascontiguousarray(arr[i, : deg[i]]) for i in range(arr.shape[0])]
 
     def get_roots_sampled_visit_count(self):
         return self._sampled_lists("visit_count")

@@ -155,7 +155,9 @@ class _SearchLoop:
             getattr(lib, "mz_policy_glue" + sfx))
         ensure_half_exp(tb._lib, dev.index if dev.index is not None else torch.cuda.current_device())
         self.model_ref = weakref.ref(model)  # the captured graph reads this model's parameters
-        self.root = torch.empty_like(hidden.reshape(B, -1))
+        # [B, cols] like the caller's hidden state; B is the loop's root count, the driver's root_capacity
+        # when it has one (the search's own hidden state may then hold fewer rows)
+        self.root = hidden.new_empty((B, hidden[0].numel()))
         self.rin = [torch.empty(n, dtype=torch.float32, device=dev) for n in (B, B, B * A, B * A, B * A)]
         # root_mode = (logits dtype code, has legal): the root preprocessing runs on the device
         # (mz_root_glue) from one packed upload of the raw root inputs; None: the host computes the
@@ -195,6 +197,8 @@ class _SearchLoop:
         self.fused_rb = hasattr(tb._lib, "mz_expand_backup_readback")
 
     def load(self, hidden, root_arrays, factor):
+        if hidden.shape[0] != self.B:
+            return self._load_padded(hidden, root_arrays, factor)
         self.root.copy_(hidden.reshape(self.B, -1))
         if self.root_mode is None:
             for t, a in zip(self.rin, root_arrays):
@@ -218,6 +222,42 @@ class _SearchLoop:
                 self.fac.copy_(factor[:, : self.cur])
             else:
                 self.fac.copy_(torch.from_numpy(np.ascontiguousarray(np.asarray(factor)[:, : self.cur], dtype=np.int32)))
+
+    def _load_padded(self, hidden, root_arrays, factor):
+        """load() for a search of n < B roots on this loop of B = root_capacity trees: the n real rows go
+        into rows [0, n) of every static buffer and rows [n, B) get a copy of row 0, so the spare trees are
+        replicas of tree 0 under other seeds: every input is finite and legal, and they raise no error
+        that tree 0 could not."""
+        n, B = hidden.shape[0], self.B
+
+        def fill(t, src):  # t: a static buffer viewed [B, per]; src: its n real rows, on the device
+            t[:n].copy_(src)
+            t[n:] = t[0]
+
+        fill(self.root, hidden.reshape(n, -1))
+        if self.root_mode is None:
+            for t, a in zip(self.rin, root_arrays):
+                fill(t.view(B, -1), torch.from_numpy(np.ascontiguousarray(a).reshape(n, -1)))
+        else:  # padded in the pinned buffer, then the one host->device copy
+            if self.raw_ev is not None:
+                self.raw_ev.synchronize()
+            dev_logits = None
+            for k, a in root_arrays.items():
+                if isinstance(a, torch.Tensor):
+                    dev_logits = a
+                    continue
+                hv = self.host_view[k].reshape(B, -1)
+                np.copyto(hv[:n], np.asarray(a).reshape(n, -1), casting="no")
+                hv[n:] = hv[0]
+            self.raw.copy_(self.raw_host, non_blocking=True)
+            self.raw_ev = torch.cuda.Event()
+            self.raw_ev.record()
+            if dev_logits is not None:
+                fill(self.dev_view["logits"].view(B, -1), dev_logits.reshape(n, -1))
+        if self.cur > 0:
+            if not isinstance(factor, torch.Tensor):
+                factor = torch.from_numpy(np.ascontiguousarray(np.asarray(factor)[:, : self.cur], dtype=np.int32))
+            fill(self.fac, factor[:, : self.cur])
 
     def run(self, model, cfg, eps, tau):
         """One search, mcts_sampled.py:106-172, all on the current stream."""
@@ -530,8 +570,24 @@ class SampledMCTS:
 
     def __init__(self, config, np_random: np.random.RandomState = None, *, lib=None, use_graph: bool = True,
                  root_shard: Tuple[int, int, int] = None, device_root: bool = True, wide_actions: bool = None,
-                 fused_transforms: bool = None, wide_supports: bool = None, later_action_cache: bool = None):
-        """`later_action_cache`: take the later agents' greedy actions of every simulation
+                 fused_transforms: bool = None, wide_supports: bool = None, later_action_cache: bool = None,
+                 root_capacity: int = None):
+        """`root_capacity` = C: every search of B <= C roots runs on the tree handle and the per-agent
+        loops (static buffers, recorded graph) of the C-root geometry, so a batch that shrinks and grows
+        (self-play searches only the environments still running, selfplay_worker.py:171-211; full-game
+        reanalysis searches len(game) roots, reanalyze_worker.py:491-611) keeps replaying one recorded
+        loop per agent instead of meeting a new geometry at every size.  The B real rows are loaded into
+        rows [0, B) of the loop's buffers and rows [B, C) are copies of row 0; the handle then reports B
+        active roots (Tree_batch.set_active_roots), so the outputs hold exactly B rows.  `np_random` is
+        consumed as by a B-root search.  Trees are independent and tree i is seeded by its index: the
+        results are rows [0, B) of the reference search over the padded C-row batch, and they equal the
+        plain B-root search bit for bit whenever row i of the model's outputs and of the transforms does
+        not depend on how many rows the batch has.  B > C raises ValueError.  None reads
+        `config.root_capacity` (off when the config has none).  Not with `root_shard`: a sharded rank's
+        tree i is seeded with its position in the whole batch, and that offset is a launch argument of the
+        prepare kernels baked into the recorded graph, so it cannot change per search.
+
+        `later_action_cache`: take the later agents' greedy actions of every simulation
         (mcts_sampled.py:136-147) from a per-node cache instead of a `model.prediction` pass on the
         selected leaves' parent states.  Such a state is row i of the `next_h` an earlier simulation
         produced, and `prediction` already ran on it there; mz_policy_glue_later keeps the later agents'
@@ -611,6 +667,20 @@ class SampledMCTS:
                 raise ValueError(f"bad root shard {root_shard}")
             root_shard = (lo, hi, total)
         self.root_shard = root_shard
+        if root_capacity is None:
+            root_capacity = getattr(config, "root_capacity", None)
+        if root_capacity is not None:
+            root_capacity = int(root_capacity)
+            if root_capacity < 1:
+                raise ValueError(f"root_capacity must be >= 1, got {root_capacity}")
+            if root_shard is not None:
+                raise ValueError(f"root_capacity={root_capacity} with root_shard={root_shard}: a rank's trees "
+                                 "are seeded from its root offset, a launch argument of the prepare kernels in "
+                                 "the recorded graph, which cannot follow a varying root count")
+            if lib is not None and not hasattr(lib, "mz_set_active_roots"):
+                raise RuntimeError("root_capacity needs a tree library with mz_set_active_roots "
+                                   "(include/mzdriver.h, product library only)")
+        self.root_capacity = root_capacity
         self.use_graph = use_graph
         # root preprocessing (softmax, masks, beta) on the device (mz_root_glue); False: in numpy on
         # the host (root_inputs), as the reference computes it
@@ -758,6 +828,10 @@ class SampledMCTS:
             raise ValueError("network_output.hidden_state must be a GPU tensor")
         dev = hidden.device
         B = hidden.shape[0]
+        # Bc: the root count of the tree handle and the loop (root_capacity, else the batch's own)
+        Bc = B if self.root_capacity is None else self.root_capacity
+        if B > Bc:
+            raise ValueError(f"batch of {B} roots exceeds root_capacity={Bc}")
 
         raw = self.root_raw(network_output, cur, legal_actions_lst, add_noise) if self.device_root else None
         if raw is not None:
@@ -767,10 +841,10 @@ class SampledMCTS:
                                                                sampled_tau)
             root_arrays, root_mode = (rr, rv, rp, rb, rn), None
         with torch.cuda.device(dev):
-            tb = self._tree(B, seed, dev)
+            tb = self._tree(Bc, seed, dev)
             # the discount is a kernel argument of the recorded launches
             key = (threading.get_ident(), id(tb), id(model), N, cur, float(eps), float(sampled_tau), float(disc),
-                   tuple(hidden.shape), hidden.dtype, root_mode, self.wide_actions, self.fused_transforms,
+                   (Bc,) + tuple(hidden.shape[1:]), hidden.dtype, root_mode, self.wide_actions, self.fused_transforms,
                    self.wide_supports, self.later_action_cache)
             with _LOCK:
                 for k in [k for k, v in _LOOPS.items() if v.model_ref() is None]:
@@ -780,7 +854,7 @@ class SampledMCTS:
                 # ids are reused once an object is freed; a recorded graph reads the parameters at the
                 # addresses it was recorded with (re-homed weights, weights.FlatWeights, need a new one)
                 if st is None or st.model_ref() is not model or st.storage != sig or st.tb is not tb:
-                    st = _LOOPS[key] = _SearchLoop(tb, B, A, N, cur, hidden, dev, model, root_mode,
+                    st = _LOOPS[key] = _SearchLoop(tb, Bc, A, N, cur, hidden, dev, model, root_mode,
                                                    wide=self.wide_actions, fused=self.fused_transforms,
                                                    wide_supports=self.wide_supports,
                                                    later_slots=S + 1 if self.later_action_cache else 0)
@@ -801,6 +875,10 @@ class SampledMCTS:
                 else:
                     st.run(model, cfg, eps, sampled_tau)  # eager (the first search also warms up)
                 st.runs += 1
+            # the handle may serve searches of other root counts (root_capacity): the getters and the
+            # consumers see this search's B rows
+            if tb.active_roots != B:
+                tb.set_active_roots(B)
 
             if _host_readback:  # :176-191 (one packed device->host copy)
                 return SearchOutput(

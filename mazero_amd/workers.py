@@ -63,11 +63,11 @@ def _device_reanalyze_decide(mcts, model, network_output, legal, policy_mask, de
     return reanalyze_policy_targets(mcts, model, network_output, legal, policy_mask, device)._asdict()
 
 
-def _default_mcts(config, np_random, root_shard, wide_actions=None, later_action_cache=None):
+def _default_mcts(config, np_random, root_shard, wide_actions=None, later_action_cache=None, root_capacity=None):
     from .mcts_sampled import SampledMCTS
 
     return SampledMCTS(config, np_random, root_shard=root_shard, wide_actions=wide_actions,
-                       later_action_cache=later_action_cache)
+                       later_action_cache=later_action_cache, root_capacity=root_capacity)
 
 
 @dataclass
@@ -82,14 +82,21 @@ class StepRecord:
     root_value: np.ndarray    # float32 [hi - lo]
     count_entropy: np.ndarray  # float64 [hi - lo, N]
     visit_entropy: np.ndarray  # float64 [hi - lo, N]
+    # SelfPlayShard.step(active=...): the environments that ran this step (sorted indices; the rows
+    # above are theirs, in this order); None when all ran
+    active: Optional[np.ndarray] = None
 
 
 class _Shard:
     def __init__(self, model, config, total: int, *, seed: int, broadcaster=None, group=None, src: int = 0,
                  make_mcts: Optional[Callable] = None, device=None, rank: Optional[int] = None,
                  world: Optional[int] = None, wide_actions: Optional[bool] = None,
-                 later_action_cache: Optional[bool] = None):
-        """`wide_actions` goes to the default search (SampledMCTS: action spaces up to 255 instead of
+                 later_action_cache: Optional[bool] = None, root_capacity: Optional[int] = None):
+        """`root_capacity` goes to the default search (SampledMCTS: every search of up to that many
+        roots on one tree handle and one set of recorded loops; None reads `config.root_capacity`).  It
+        needs world == 1, where the shard builds its search without a root shard (the whole batch is the
+        shard): SampledMCTS refuses it together with a root shard.
+        `wide_actions` goes to the default search (SampledMCTS: action spaces up to 255 instead of
         64; None reads `config.wide_actions`), and so does `later_action_cache` (the later agents'
         greedy actions from a per-node cache; None reads `config.later_action_cache`); a `make_mcts` of
         the caller's decides for itself."""
@@ -105,7 +112,11 @@ class _Shard:
         # the same generator state on every rank: sharded draws are sliced from whole-batch draws
         self.np_random = np.random.RandomState(seed)
         self.broadcaster, self.src, self.group = broadcaster, src, group
-        self.make_mcts = make_mcts or (lambda c, r, s: _default_mcts(c, r, s, wide_actions, later_action_cache))
+        self.make_mcts = make_mcts or (lambda c, r, s: _default_mcts(c, r, s, wide_actions, later_action_cache,
+                                                                     root_capacity))
+        if root_capacity is None:
+            root_capacity = getattr(config, "root_capacity", None)
+        self.root_capacity = root_capacity
         self.device = device
         self.model_index = -1
         if broadcaster is not None and self.rank == src and broadcaster.model_index < 0:
@@ -116,6 +127,13 @@ class _Shard:
     @property
     def root_shard(self):
         return (self.lo, self.hi, self.total)
+
+    def _search_shard(self):
+        """The root shard the search is built with: None for a capacity search on a single rank (the
+        whole batch is the shard, so the draws and the tree seeds are those of (0, total, total))."""
+        if self.root_capacity is not None and self.world == 1:
+            return None
+        return self.root_shard
 
     def _sync(self) -> int:
         if self.broadcaster is not None:
@@ -149,31 +167,55 @@ class SelfPlayShard(_Shard):
         self.decide = decide or _device_selfplay_decide
 
     def step(self, t: int, obs, legal, *, temperature: float = 1.0, sampled_tau: float = 1.0,
-             greedy_epsilon: float = 0.0, eps_uniforms=None) -> StepRecord:
+             greedy_epsilon: float = 0.0, eps_uniforms=None, active=None) -> StepRecord:
         """One environment step of this rank's environments.  `obs` / `legal` are the shard's rows;
-        `eps_uniforms` (u_eps [N, total], u_cat [N, total]) are whole-batch draws, sliced here."""
+        `eps_uniforms` (u_eps [N, total], u_cat [N, total]) are whole-batch draws, sliced here.
+
+        `active`: the sorted indices of the environments still running (selfplay_worker.py:171); `obs`,
+        `legal` and `eps_uniforms` then hold those rows only and the step searches len(active) roots, as
+        the reference does (:180-211).  The search is built without a root shard, so the per-root draws
+        are made for the active rows.  Single rank only: on a sharded rank tree i must be seeded with its
+        position in the whole active list, and the rank's root offset is a launch argument of the prepare
+        kernels baked into the recorded graph, so it cannot change per step."""
+        if active is not None:
+            if self.world > 1:
+                raise NotImplementedError(
+                    "SelfPlayShard.step(active=...) with world > 1: tree i is seeded with its position in the "
+                    "whole active list, so the rank's root offset would change per step, and that offset is a "
+                    "launch argument of the prepare kernels baked into the recorded graph")
+            active = np.asarray(active, dtype=np.int64).reshape(-1)
+            if active.size < 1 or (np.diff(active) <= 0).any() or active[0] < 0 or active[-1] >= self.total:
+                raise ValueError(f"active must be sorted, distinct indices in [0, {self.total})")
         idx = self._sync()  # _update_model_before_step, selfplay_worker.py:176-177
         net_out = self._initial_inference(obs)
-        mcts = self.make_mcts(self.config, self.np_random, self.root_shard)  # :187
-        if eps_uniforms is not None:
-            eps_uniforms = tuple(np.asarray(u)[:, self.lo:self.hi] for u in eps_uniforms)
+        if active is not None:
+            mcts = self.make_mcts(self.config, self.np_random, None)
+        else:
+            mcts = self.make_mcts(self.config, self.np_random, self._search_shard())  # :187
+            if eps_uniforms is not None:
+                eps_uniforms = tuple(np.asarray(u)[:, self.lo:self.hi] for u in eps_uniforms)
         d = self.decide(mcts, self.model, net_out, self.num_agents, legal, temperature=temperature,
                         sampled_tau=sampled_tau, greedy_epsilon=greedy_epsilon, eps_uniforms=eps_uniforms,
                         device=self.device)
         return StepRecord(t, idx, self.lo, _to_np(d["actions"]).astype(np.int32), _to_np(d["prob_action"]),
                           _to_np(d["root_value"]).reshape(-1), _to_np(d["count_entropy"]),
-                          _to_np(d["visit_entropy"]))
+                          _to_np(d["visit_entropy"]), active)
 
     def run(self, env: Callable, steps: int, *, learner: Optional[Callable] = None, eps_uniforms: Callable = None,
             **step_kw) -> List[StepRecord]:
-        """`steps` environment steps.  env(t, lo, hi) -> (obs, legal) for environments [lo, hi);
-        learner(model, t) on the source rank after step t -> the trained-steps counter to publish
-        (or None); eps_uniforms(t) -> whole-batch (u_eps, u_cat) or None."""
+        """`steps` environment steps.  env(t, lo, hi) -> (obs, legal) for environments [lo, hi), or
+        (obs, legal, active) with the rows of the environments `active` still running (see step; None:
+        all of them); learner(model, t) on the source rank after step t -> the trained-steps counter to
+        publish (or None); eps_uniforms(t) -> whole-batch (u_eps, u_cat) or None, sliced to the active
+        environments here."""
         out = []
         for t in range(steps):
-            obs, legal = env(t, self.lo, self.hi)
-            out.append(self.step(t, obs, legal, eps_uniforms=None if eps_uniforms is None else eps_uniforms(t),
-                                 **step_kw))
+            obs, legal, *rest = env(t, self.lo, self.hi)
+            active = rest[0] if rest else None
+            u = None if eps_uniforms is None else eps_uniforms(t)
+            if u is not None and active is not None:
+                u = tuple(np.asarray(x)[:, np.asarray(active, dtype=np.int64)] for x in u)
+            out.append(self.step(t, obs, legal, eps_uniforms=u, active=active, **step_kw))
             self._publish(learner, t)
         return out
 
@@ -193,7 +235,7 @@ class ReanalyzeShard(_Shard):
         """obs / legal / policy_mask: this rank's rows [lo, hi) of the batch."""
         idx = self._sync()
         net_out = self._initial_inference(obs)
-        mcts = self.make_mcts(self.config, self.np_random, self.root_shard)
+        mcts = self.make_mcts(self.config, self.np_random, self._search_shard())
         out = self.decide(mcts, self.model, net_out, legal, policy_mask, self.device)
         out = {k: _to_np(v) for k, v in out.items()}
         out["model_index"] = idx
@@ -215,7 +257,7 @@ class ReanalyzeShard(_Shard):
             raise ValueError(f"{len(pos)} trajectories x {int(num_unroll_steps) + 1} rows != {self.total} roots")
         idx = self._sync()
         net_out = self._initial_inference(obs)
-        mcts = self.make_mcts(self.config, self.np_random, self.root_shard)
+        mcts = self.make_mcts(self.config, self.np_random, self._search_shard())
         from .consume import reanalyze_value_targets
 
         r, v = reanalyze_value_targets(
