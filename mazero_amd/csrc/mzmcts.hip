@@ -202,19 +202,30 @@ __host__ __device__ __forceinline__ unsigned span_n(unsigned n, unsigned k = 0) 
 // arrays, whose offsets follow from B, PS and B * P (computed while the header load is in flight).
 constexpr unsigned kArenaHdr = (unsigned)((sizeof(Params) + 64 + 255) / 256);
 __host__ __device__ __forceinline__ unsigned arena_lp(unsigned B) { return kArenaHdr + B + 1; }  // (span of B * 256 bytes)
+// The node arrays' spans are multiples of one unit c, the span of a 4-byte array (the 16-byte arrays
+// take 4 c, at most 768 bytes more than their own span): every node array is at o_A plus a constant
+// multiple of c (kNodeSpan*).  k_chain3 gets o_A and c packed in one preloaded argument dword and
+// computes no round-up on the way to a record (arena_pack).
+__host__ __device__ __forceinline__ unsigned arena_unit(unsigned nodes) { return span_n<4>(nodes); }
+constexpr unsigned kNodeSpanPar = 4, kNodeSpanBn = 5, kNodeSpanQ = 9, kNodeSpanPP = 10, kNodeSpanC = 11, kNodeSpanEnd = 15;
+__host__ __device__ __forceinline__ void arena_nodes_at(Dev &d, unsigned o_A, unsigned c) {
+    d.o_A = o_A;
+    d.o_Par = o_A + kNodeSpanPar * c;
+    d.o_Bn = o_A + kNodeSpanBn * c;
+    d.o_Q = o_A + kNodeSpanQ * c;
+    d.o_PP = o_A + kNodeSpanPP * c;
+    d.o_C = o_A + kNodeSpanC * c;
+    d.o_stats = o_A + kNodeSpanEnd * c;  // (what follows the node arrays: arena_hot)
+}
 __host__ __device__ __forceinline__ void arena_nodes(Dev &d, unsigned B, unsigned P, unsigned PS) {
-    const unsigned nodes = B * P;
-    const unsigned s16 = span_n<16>(nodes), s4 = span_n<4>(nodes);
     d.o_hdr = kArenaHdr;
     d.o_lp = arena_lp(B);
-    d.o_A = d.o_lp + span_n<4>(PS + 1 + kWave);
-    d.o_Par = d.o_A + s16;
-    d.o_Bn = d.o_Par + s4;
-    d.o_Q = d.o_Bn + s16;
-    d.o_PP = d.o_Q + s4;
-    d.o_C = d.o_PP + s4;
-    d.o_stats = d.o_C + s16;  // (what follows the node arrays: arena_hot)
+    arena_nodes_at(d, d.o_lp + span_n<4>(PS + 1 + kWave), arena_unit(B * P));
 }
+// o_A and c in 16 bits each, k_chain3's packed argument.  A handle whose geometry fits has its node
+// arrays end below (65535 + 15 * 65535) * 256 bytes < 4 GiB: 32-bit byte offsets off the arena base.
+__host__ __device__ __forceinline__ bool arena_packs(unsigned o_A, unsigned c) { return o_A < 65536u && c < 65536u; }
+__host__ __device__ __forceinline__ unsigned arena_pack(unsigned o_A, unsigned c) { return o_A | (c << 16); }
 // pUCT coefficient table entries, T[n (n + 1) / 2 + v] = pb_c(n, v) for n < PS, padded to 4.  Only
 // k_step's LDS-staged table (4 TT <= kTableLdsMax: PS <= 155) and k_tree's prior scores (value
 // entries E <= kBkCap: PS <= 342) read past T[0]; every other kernel computes pb_c from the
@@ -3372,9 +3383,13 @@ __global__ __launch_bounds__(128) void k_chain(char *base, const float *policy, 
 // Every error and output is decided from the same scalar inputs as k_chain: results are bit-identical.
 //
 // Launch arguments.  The first 14 dwords arrive preloaded in SGPRs; they hold everything round 1
-// addresses: tree t's header is a 256-byte block at a constant offset, the lambda-power table and
-// the node arrays follow at offsets computed from B, PS and B * P (arena_nodes) while the header
-// load is in flight.  The rest (ChainIO) is read through the kernel-argument pointer by the waves
+// addresses: tree t's header is a 256-byte block at a constant offset, the lambda-power table
+// follows the headers (arena_lp), and the node arrays are at o_A plus constant multiples of the unit
+// c (arena_nodes_at), both packed in the argument apk (arena_pack): no role computes a round-up to
+// reach a record, and every record is addressed as the arena base plus a 32-bit byte offset.
+// The kernel's first instructions test the wave index: each role then computes only what its first
+// loads address and issues them; P, PS, the hsx range test and the rest follow behind the issue.
+// The rest (ChainIO) is read through the kernel-argument pointer by the waves
 // that need it, where they need it: the compiler would otherwise load every argument in the common
 // prologue and wait there.  ChainIO is two 64-byte lines, one scalar load each: wave 2's (the row
 // gather's arguments) and wave 0's (the output pointers), each with the handle constants that role
@@ -3388,7 +3403,7 @@ struct ChainK {  // the Params fields wave 0 reads (mz_create checks them agains
     unsigned o_R, o_err, o_D, o_stats;
     float delta;
     unsigned o_pb, o_sq;
-    int pad_;
+    float discount;  // (the launch's: waves 0 and 1 read it here, it is not among the preloaded dwords)
 };
 struct ChainIO {
     // wave 2's line
@@ -3405,12 +3420,11 @@ struct ChainIO {
 struct Chain3Args {  // k_chain3's parameter list, for the kernel-argument offset of ChainIO
     char *base;
     const float *policy, *beta, *reward, *value;
-    int ppk, bak, hsx;
-    float discount;
+    int ppk, bak, hsx, apk;
     const char *src_slot;
     ChainIO io;
 };
-// (the first 14 dwords, through the discount, arrive preloaded in SGPRs: two of the 16 user SGPRs
+// (the first 14 dwords, through apk, arrive preloaded in SGPRs: two of the 16 user SGPRs
 // hold the kernel-argument pointer.  src_slot is not among them: wave 2 fetches it with a scalar
 // load and waits for it before it issues the row's loads)
 static_assert(offsetof(Chain3Args, src_slot) == 56 && offsetof(Chain3Args, io) == 64 && sizeof(ChainIO) == 128 &&
@@ -3437,33 +3451,38 @@ __device__ __forceinline__ void st_lane16(uintptr_t p, int4v v) { *(g_int4v *)p 
 __device__ __forceinline__ void st_lane4(uintptr_t p, int v) { *(g_int *)p = v; }
 // scalar loads issued here and waited for by swait (invisible to the compiler's wait counting, which
 // stays correct: its own LDS waits only ever wait longer with more loads outstanding)
+template <int OFF = 0>  // (an immediate byte offset)
 __device__ __forceinline__ int sload1(const void *p) {
     int v;
-    asm volatile("s_load_dword %0, %1, 0x0" : "=s"(v) : "s"(p) : "memory");
+    asm volatile("s_load_dword %0, %1, %2" : "=s"(v) : "s"(p), "n"(OFF) : "memory");
     return v;
 }
 typedef int int2v __attribute__((ext_vector_type(2)));
+template <int OFF = 0>  // (an immediate byte offset)
 __device__ __forceinline__ int2v sload2(const void *p) {
     int2v v;
-    asm volatile("s_load_dwordx2 %0, %1, 0x0" : "=s"(v) : "s"(p) : "memory");
+    asm volatile("s_load_dwordx2 %0, %1, %2" : "=s"(v) : "s"(p), "n"(OFF) : "memory");
     return v;
 }
 __device__ __forceinline__ uintptr_t u64_of(int lo, int hi) {
     return (uintptr_t)(((unsigned long long)(unsigned)hi << 32) | (unsigned)lo);
 }
+template <int OFF = 0>  // (an immediate byte offset)
 __device__ __forceinline__ int4v sload4(const void *p) {
     int4v v;
-    asm volatile("s_load_dwordx4 %0, %1, 0x0" : "=s"(v) : "s"(p) : "memory");
+    asm volatile("s_load_dwordx4 %0, %1, %2" : "=s"(v) : "s"(p), "n"(OFF) : "memory");
     return v;
 }
+template <int OFF = 0>  // (an immediate byte offset)
 __device__ __forceinline__ int8v sload8(const void *p) {
     int8v v;
-    asm volatile("s_load_dwordx8 %0, %1, 0x0" : "=s"(v) : "s"(p) : "memory");
+    asm volatile("s_load_dwordx8 %0, %1, %2" : "=s"(v) : "s"(p), "n"(OFF) : "memory");
     return v;
 }
+template <int OFF = 0>  // (an immediate byte offset)
 __device__ __forceinline__ int16v sload16(const void *p) {
     int16v v;
-    asm volatile("s_load_dwordx16 %0, %1, 0x0" : "=s"(v) : "s"(p) : "memory");
+    asm volatile("s_load_dwordx16 %0, %1, %2" : "=s"(v) : "s"(p), "n"(OFF) : "memory");
     return v;
 }
 
@@ -3522,18 +3541,43 @@ __device__ __forceinline__ double draw_u(unsigned n0, unsigned n1) {
 }
 template <int NC, bool SEL, int ROW, bool W4>
 __global__ __launch_bounds__(W4 ? 256 : 192) void k_chain3(char *base, const float *policy, const float *beta, const float *reward,
-                                                const float *value, int ppk, int bak, int hsx, float discount,
+                                                const float *value, int ppk, int bak, int hsx, int apk,
                                                 const char *src_slot, ChainIO io) {
     static_assert(NC >= kWave && NC % kWave == 0 && NC < 1024, "k_chain3 node classes are whole waves, < 1024");
     (void)io;  // (read through the kernel-argument pointer, see above)
     constexpr int NCH = NC / kWave;  // node chunks of one wave
     constexpr Chain3Layout<NC> L(NC);
-    const int P = ppk & 0x3ff, PS = (ppk >> 10) & 0x3ff;
-    const int A = (bak >> 24) & 0x7f, fast_ok = (int)((unsigned)bak >> 31);
+    // The 16 KiB row class (ROW 2) keeps the entry this kernel had before the role-first one, line for
+    // line: the role tests in the order 3, 1, 2, the node arrays' offsets by arena_nodes while the
+    // header load is in flight, masked record loads through 64-bit addresses, and the discount in the
+    // 14th preloaded dword -- in these instantiations apk carries the discount's bits
+    // (launch_chain3_row).  There wave 2 issues sixteen LDS-DMA loads ahead of the start barrier, and
+    // with the role-first entry 27m K = 1 measured 3.2 % slower whatever the order of the role tests
+    // (profiles/chain3_entry).
+    constexpr bool kEntry = ROW != 2;
+    // (stamped builds: every role's phases count from its wave's first instruction)
+    unsigned long long ts[8] = {0};
+    stamp(ts, 0);
+    const unsigned long long rt0 = span_open();
+    // The role first: the wave index is tested in the kernel's first instructions, each role's body
+    // lies out of line behind one taken branch (wave 0 falls through), and what follows here is
+    // computed by the role that uses it, behind its first loads' issue -- nothing but the role test
+    // is common to the four waves.
+    const int wv = uni((int)(threadIdx.x >> 6));
+    // (one compare and one branch per role: the empty asm keeps the compiler from folding the tests
+    // into a search over the wave index with flag registers)
+    auto role = [&](int r) {
+        int w = wv;
+        asm volatile("" : "+s"(w));
+        return w == r;
+    };
+    const int t = blockIdx.x;
+    const int l = threadIdx.x & (kWave - 1);
     Dev d;
     d.base = (gchar *)base;
-    // the node arrays' offsets, computed by each role after it has issued its header load (the
-    // empty asm orders the arithmetic behind the loads' asm statements)
+    d.o_hdr = kArenaHdr;
+    // (!kEntry) the node arrays' offsets, computed by each role after it has issued its header load
+    // (the empty asm orders the arithmetic behind the loads' asm statements)
     auto arena = [&]() {
         int bk = bak, pk = ppk;
         asm volatile("" : "+s"(bk), "+s"(pk));
@@ -3548,26 +3592,50 @@ __global__ __launch_bounds__(W4 ? 256 : 192) void k_chain3(char *base, const flo
     float *sPP = (float *)(smem + L.oPP);
     float *sRv = (float *)(smem + L.oRv);
     float *sBv = (float *)(smem + L.oBv);
-    const int t = blockIdx.x;
-    const int l = threadIdx.x & (kWave - 1);
-    const int wv = uni((int)(threadIdx.x >> 6));
-    const size_t nb = (size_t)t * P;
-    unsigned long long ts[8] = {0};
-    stamp(ts, 0);
-    const unsigned long long rt0 = span_open();
-    d.o_hdr = kArenaHdr;
-    TreeHdr *hp = d.hdr() + t;
-    const int Dp = (hsx >= 0 && hsx + 1 <= P) ? hsx : 0;  // the chain's leaf, if the header agrees
+    // tree t's header block: 32-bit arithmetic (t < B < o_A < 65536, arena_packs) and, in the scalar
+    // loads, the headers' offset as the instruction's immediate
+    constexpr int kHdr8 = (int)kArenaHdr * 256;
+    auto hb_of = [&]() { return (const gchar *)d.base + ((unsigned)t << 8); };
+    auto hdr_of = [&](const gchar *hb) { return (TreeHdr *)(gchar *)(hb + kHdr8); };
+    // (likewise the launch's inputs: t * A * 4 < 2^25)
+    auto in_t = [&](const float *p) { return (const void *)((const gchar *)p + ((unsigned)t << 2)); };
+    auto in_row = [&](const float *p, int A) {
+        return *(const float *)((const gchar *)p + (((unsigned)t * (unsigned)A + (unsigned)(l < A ? l : 0)) << 2));
+    };
+    const void *ka = (const void *)__builtin_amdgcn_kernarg_segment_ptr();
+    constexpr int kIo = (int)offsetof(Chain3Args, io);
+    // the node arrays as 32-bit byte offsets off the arena base, from the packed argument (arena_pack:
+    // the arrays end below 4 GiB)
+    auto oA8_of = [&]() { return ((unsigned)apk & 0xffffu) << 8; };
+    auto c8_of = [&]() { return ((unsigned)apk >> 16) << 8; };
+    auto P_of = [&]() { return ppk & 0x3ff; };
+    auto PS_of = [&]() { return (ppk >> 10) & 0x3ff; };
+    auto A_of = [&]() { return (bak >> 24) & 0x7f; };
+    // the chain's leaf, if the header agrees
+    auto Dp_of = [&](int P) { return (hsx >= 0 && hsx + 1 <= P) ? hsx : 0; };
+    // "not a chain", the one predicate of waves 0, 1 and 2 (all three read the same header).  A depth
+    // below 0 counts as out of range: wave 1's record loads clamp their lane to D as unsigned.
+    auto no_chain = [&](int D, int P, int toth, int leafh) {
+        return (kEntry ? (unsigned)D >= (unsigned)P : D + 1 > P) || toth != D + 1 || leafh != D;
+    };
 
-    if constexpr (W4) {
-        if (wv == 3) {
+    auto wave3 = [&]() {
+        if constexpr (W4) {
+            const int A = A_of();
             // ======== wave 3: the expansion's distribution and draw (cnode.cpp:224-295) ========
             // Straight-line code: this launch's beta row and the header's two engine words, the
             // start barrier while they are in flight, the distribution, one LDS store.  No header
             // check (on a dead or out-of-chain tree wave 0 returns before it reads the slot; the
             // loads are in bounds for every t), no global store.
-            const float bet = beta[(size_t)t * A + (l < A ? l : 0)];
-            int2v nx = sload2(&hp->nxt[0]);
+            float bet;
+            int2v nx;
+            if constexpr (kEntry) {
+                bet = in_row(beta, A);
+                nx = sload2<kHdr8 + (int)offsetof(TreeHdr, nxt)>(hb_of());
+            } else {
+                bet = beta[(size_t)t * A + (l < A ? l : 0)];
+                nx = sload2(&(d.hdr() + t)->nxt[0]);
+            }
             start_barrier();
             asm volatile("s_waitcnt lgkmcnt(0)" : "+s"(nx) : : "memory");
             int a = 0;
@@ -3583,46 +3651,84 @@ __global__ __launch_bounds__(W4 ? 256 : 192) void k_chain3(char *base, const flo
                 draw_slot_set(sXi, (int)(0x80000000u | (unsigned)a));
             }
             wait_lds();
-            return;
         }
-    }
+    };
 
-    if (wv == 1) {
+    auto wave1 = [&]() {
         // ======== wave 1: CTree::back_propagate (cnode.cpp:415-450) over the chain ========
-        int8v hv = sload8(hp);  // cursor, tot, D, err, mm_min, mm_max, mm_cnt, leaf
-        int r_i = sload1(reward + t), v_i = sload1(value + t);
-        arena();
-        const float *lpt = d.lp();
+        const int P = P_of(), Dp = Dp_of(P);
+        TreeHdr *hp;
+        int8v hv;  // cursor, tot, D, err, mm_min, mm_max, mm_cnt, leaf
+        int r_i, v_i, g_i = apk;  // (!kEntry: apk is the discount)
+        // The chain's records, lane i = node i: the arena base in a scalar pair plus a 32-bit byte
+        // offset per lane, the arrays' offsets from the packed argument (no round-up, no 64-bit
+        // address arithmetic in front of the loads)
+        unsigned rA = 0, rC = 0, rPP = 0, rLp = 0;  // A[nb], C[nb], PP[nb], lp[0]
+        const size_t nb = (size_t)t * P;            // (!kEntry)
+        const float *lpt = nullptr;                 // (!kEntry)
+        if constexpr (kEntry) {
+            const gchar *hb = hb_of();
+            hp = hdr_of(hb);
+            hv = sload8<kHdr8>(hb);
+            r_i = sload1(in_t(reward)), v_i = sload1(in_t(value));
+            g_i = sload1<kIo + (int)(offsetof(ChainIO, k) + offsetof(ChainK, discount))>(ka);
+            const unsigned oA8 = oA8_of(), c8 = c8_of(), nbu = (unsigned)t * (unsigned)P;
+            rA = oA8 + nbu * 16, rC = rA + kNodeSpanC * c8;
+            rPP = oA8 + kNodeSpanPP * c8 + nbu * 4;
+            rLp = arena_lp((unsigned)bak & 0xffffffu) << 8;
+        } else {
+            hp = d.hdr() + t;
+            hv = sload8(hp);
+            r_i = sload1(reward + t), v_i = sload1(value + t);
+            arena();
+            lpt = d.lp();
+        }
+        const gchar *ab = d.base;
         int4 a4[NCH];
         float2 cw[NCH];
         float pp[NCH], lpv[NCH];
-        auto load = [&](int D, const float *lp) {
+        auto load = [&](int D) {
 #pragma unroll
             for (int c = 0; c < NCH; ++c) {
-                const int i = c * kWave + l;
-                a4[c] = make_int4(0, 0, 0, 0);
-                cw[c] = make_float2(0.f, 0.f);
-                pp[c] = 0.f;
-                lpv[c] = 0.f;
-                if (i <= D) {
-                    a4[c] = d.A()[nb + i];
-                    cw[c] = *(const float2 *)&d.C()[nb + i];
-                    pp[c] = d.PP()[nb + i];
-                    lpv[c] = lp[D - i];  // lambda^(D - i): this back-propagation's depth at node i
+                if constexpr (kEntry) {
+                    // (lanes past the leaf load the leaf's records: in bounds and never read, where a
+                    // test would put an exec mask and eight register clears in front of the loads)
+                    const unsigned i = (unsigned)(c * kWave + l), ic = i < (unsigned)D ? i : (unsigned)D;
+                    a4[c] = *(const int4 *)(ab + (rA + ic * 16));
+                    cw[c] = *(const float2 *)(ab + (rC + ic * 16));
+                    pp[c] = *(const float *)(ab + (rPP + ic * 4));
+                    lpv[c] = *(const float *)(ab + (rLp + ((unsigned)D - ic) * 4));  // lambda^(D - i): this back-propagation's depth at node i
+                } else {
+                    const int i = c * kWave + l;
+                    a4[c] = make_int4(0, 0, 0, 0);
+                    cw[c] = make_float2(0.f, 0.f);
+                    pp[c] = 0.f;
+                    lpv[c] = 0.f;
+                    if (i <= D) {
+                        a4[c] = d.A()[nb + i];
+                        cw[c] = *(const float2 *)&d.C()[nb + i];
+                        pp[c] = d.PP()[nb + i];
+                        lpv[c] = lpt[D - i];
+                    }
                 }
             }
         };
-        load(Dp, lpt);  // (one round: every address follows from the preloaded arguments)
-        asm volatile("s_waitcnt lgkmcnt(0)" : "+s"(hv), "+s"(r_i), "+s"(v_i)::"memory");
+        load(Dp);  // (one round: every address follows from the preloaded arguments)
+        if constexpr (kEntry) asm volatile("s_waitcnt lgkmcnt(0)" : "+s"(hv), "+s"(r_i), "+s"(v_i), "+s"(g_i)::"memory");
+        else asm volatile("s_waitcnt lgkmcnt(0)" : "+s"(hv), "+s"(r_i), "+s"(v_i)::"memory");
         if constexpr (W4) start_barrier();  // (every wave, before any return: wave 0's slot clear)
         const float r_in = i2f(r_i), v_in = i2f(v_i);
         const int herr = hv[3], D = hv[2], toth = hv[1], leafh = hv[7];
         if (herr) return;  // (wave 0 reports; no wave takes the barrier on the error paths)
         if (D != Dp || toth != D + 1 || leafh != D) {
-            if (D + 1 > P || toth != D + 1 || leafh != D) return;  // not a chain (wave 0 reports)
-            load(D, lpt);  // a graph replayed out of sequence: the header's chain
+            if (no_chain(D, P, toth, leafh)) return;  // (wave 0 reports)
+            load(D);  // a graph replayed out of sequence: the header's chain
         }
-        const float g = discount;
+        if constexpr (kEntry) {  // (the whole record in one 16-byte load: its third word is not read)
+#pragma unroll
+            for (int c = 0; c < NCH; ++c) asm volatile("" : : "v"(a4[c].z));
+        }
+        const float g = i2f(g_i);
         // the chain's rewards, reversed: sRv[j] = r_{D-j} (r_D = this simulation's reward)
 #pragma unroll
         for (int c = 0; c < NCH; ++c) {
@@ -3682,8 +3788,13 @@ __global__ __launch_bounds__(W4 ? 256 : 192) void k_chain3(char *base, const flo
                 const float ws = cw[c].x + lpv[c] * key;
                 const float val = ws / tw;
                 const int4 na = make_int4(a4[c].x + 1, a4[c].y, f2i(val), f2i(rw));
-                d.A()[nb + i] = na;
-                *(float2 *)&d.C()[nb + i] = make_float2(ws, tw);
+                if constexpr (kEntry) {
+                    *(int4 *)(d.base + (rA + (unsigned)i * 16)) = na;
+                    *(float2 *)(d.base + (rC + (unsigned)i * 16)) = make_float2(ws, tw);
+                } else {
+                    d.A()[nb + i] = na;
+                    *(float2 *)&d.C()[nb + i] = make_float2(ws, tw);
+                }
                 sA[i] = na;
                 sPP[i] = pp[c];
                 if (i >= 1) {
@@ -3716,10 +3827,9 @@ __global__ __launch_bounds__(W4 ? 256 : 192) void k_chain3(char *base, const flo
         // launch is unchanged, 3.10 us: wave 0 ends last either way, profiles/round6/ab)
         wait_lds();
         span_end(hsx, 1);
-        return;
-    }
+    };
 
-    if (wv == 2) {
+    auto wave2 = [&]() {
         // ======== wave 2: the leaf-row gather and the counters ========
         // Straight-line code in issue order (the row class ROW is a template argument): every wait
         // the compiler places then counts exactly the loads issued after the one it needs.
@@ -3743,19 +3853,25 @@ __global__ __launch_bounds__(W4 ? 256 : 192) void k_chain3(char *base, const flo
                 for (int k = 0; k < 16; ++k) glds16a(srow + (o + 1024 * k < lst ? o + 1024 * k : lst), sbig + 1024 * k);
             }
         }
-        int16v hv = sload16(hp);  // cursor, tot, D, err, mm_min, mm_max, mm_cnt, leaf, tame, root_vis, leaf_y, hot_tag
+        // cursor, tot, D, err, mm_min, mm_max, mm_cnt, leaf, tame, root_vis, leaf_y, hot_tag
+        int16v hv = kEntry ? sload16<kHdr8>(hb_of()) : sload16(d.hdr() + t);
         // pool, pool_stride, row_bytes, gather_out, one_minus_rho, o_stats (wave 2's argument line)
-        int16v io8 = sload16((const void *)iop);
+        int16v io8 = kEntry ? sload16<kIo>(ka) : sload16((const void *)iop);
         // (every wave takes the start barrier before any return: wave 0's slot clear.  Here ahead of
         // the wait: this wave's round 1 is two dependent scalar round trips with ROW 1, 2, and the
         // other waves would wait at the barrier for the second)
         if constexpr (W4) start_barrier();
         asm volatile("s_waitcnt lgkmcnt(0)" : "+s"(io8), "+s"(hv) : : "memory");
         const int omri = io8[8], osti = io8[9];
+        const int P = P_of(), PS = PS_of();
         int rv0 = hv[9];
         if (hv[11] != hv[1]) {  // no valid hot copy: the root's record
-            arena();
-            rv0 = uni(d.A()[nb].x);
+            if constexpr (kEntry) {
+                rv0 = uni(*(const int *)(d.base + (oA8_of() + (unsigned)t * (unsigned)P * 16)));
+            } else {
+                arena();
+                rv0 = uni(d.A()[(size_t)t * P].x);
+            }
         }
         stamp(ts, 1);
         // (typed as global memory: flat accesses would count against lgkmcnt too)
@@ -3772,7 +3888,7 @@ __global__ __launch_bounds__(W4 ? 256 : 192) void k_chain3(char *base, const flo
         const long long st_old = st[l < MZ_S_CYC_HEADER ? l : 0];
         // a dead or inconsistent tree: wave 0 reports; no wave takes the barrier on these paths (all
         // three read the same header)
-        if (herr || D + 1 > P || toth != D + 1 || leafh != D) {
+        if (herr || no_chain(D, P, toth, leafh)) {
             wait_vm();  // (no LDS-DMA may land after the workgroup ends)
             return;
         }
@@ -3831,32 +3947,99 @@ __global__ __launch_bounds__(W4 ? 256 : 192) void k_chain3(char *base, const flo
         }
         if constexpr (ROW == 2) wait_vm();
         span_end(hsx, 2);
-        return;
+    };
+
+    // The role tests.  Wave 2 first: with a row to gather its round 1 is two dependent round trips
+    // (src_slot, then the row's loads, issued ahead of the start barrier), so it is the last wave at
+    // the barrier and the other three wait there for it.  Then the waves of the two arms, the
+    // back-propagation and the draw; wave 0 falls through.
+    if constexpr (kEntry) {
+        if (__builtin_expect_with_probability(role(2), 0, 0.7)) {
+            wave2();
+            return;
+        }
+        if (__builtin_expect_with_probability(role(1), 0, 0.7)) {
+            wave1();
+            return;
+        }
+        if (W4 && __builtin_expect_with_probability(role(3), 0, 0.7)) {
+            wave3();
+            return;
+        }
+    } else {
+        // The common prologue of the earlier entry: what every role derives from the preloaded
+        // arguments, computed once ahead of the role tests.  The roles' lambdas name the same
+        // expressions (P_of() and the rest), so the compiler reuses these values there; without the
+        // empty asm, which uses them here, it would sink each computation into the roles instead.
+        const int P = P_of(), PS = PS_of(), A = A_of(), Dp = Dp_of(P);
+        const size_t nb = (size_t)t * P;
+        TreeHdr *hp = d.hdr() + t;
+        asm volatile("" : : "s"(P), "s"(PS), "s"(A), "s"(Dp), "s"(nb), "s"(hp));
+        if (W4 && wv == 3) {
+            wave3();
+            return;
+        }
+        if (wv == 1) {
+            wave1();
+            return;
+        }
+        if (wv == 2) {
+            wave2();
+            return;
+        }
     }
 
     // ======== wave 0: CTree::expand (cnode.cpp:224-295) of the leaf: one draw ========
+    const int A = A_of();
+    const int P = P_of(), PS = PS_of(), Dp = Dp_of(P), fast_ok = (int)((unsigned)bak >> 31);
+    const size_t nb = (size_t)t * P;
+    TreeHdr *hp;
     // cursor, tot, D, err, mm_min, mm_max, mm_cnt, leaf, tame, root_vis, leaf_y, hot_tag, nxt[0 .. 3]
-    int16v hv = sload16(hp);
+    int16v hv;
     // idx_x, idy, act and the handle's constants (wave 0's argument line: ChainIO, ChainK)
-    int16v kv = sload16((const char *)iop + offsetof(ChainIO, idx_x));
-    int r_i = sload1(reward + t), v_i = sload1(value + t);
-    const float pol = policy[(size_t)t * A + (l < A ? l : 0)];
-    const float bet = beta[(size_t)t * A + (l < A ? l : 0)];
+    int16v kv;
+    int r_i, v_i;
+    float pol, bet;
+    if constexpr (kEntry) {
+        const gchar *hb = hb_of();
+        hp = hdr_of(hb);
+        hv = sload16<kHdr8>(hb);
+        kv = sload16<kIo + (int)offsetof(ChainIO, idx_x)>(ka);
+        r_i = sload1(in_t(reward)), v_i = sload1(in_t(value));
+        pol = in_row(policy, A), bet = in_row(beta, A);
+    } else {
+        hp = d.hdr() + t;
+        hv = sload16(hp);
+        kv = sload16((const char *)iop + offsetof(ChainIO, idx_x));
+        r_i = sload1(reward + t), v_i = sload1(value + t);
+        pol = policy[(size_t)t * A + (l < A ? l : 0)];
+        bet = beta[(size_t)t * A + (l < A ? l : 0)];
+    }
     if constexpr (W4) {  // the hand-over slot, cleared ahead of the start barrier (round 1's wait covers the store)
         if (l == 0) draw_slot_set(sXi, 0);
     }
-    arena();
     // This launch's record stores, one per lane, from addresses held in registers: lane 0 the child's
     // C, lane 1 the leaf's Bn, lane 2 the child's A, lane 3 the child's Bn (16 bytes each), and the
     // dwords of lane 0 the child's PP, lanes 1-3 idx_x / idy / act.  The node addresses follow from
     // the preloaded arguments (the leaf of an in-sequence launch is hsx): computed here, while round
     // 1's loads are in flight, in vector registers (the scalar file is full).
-    unsigned oA = d.o_A, oBn = d.o_Bn, oC = d.o_C;
-    asm volatile("" : "+s"(oA), "+s"(oBn), "+s"(oC));  // (values, not fields: no table in scratch)
-    const unsigned o16 = (l == 0) ? oC : (l == 2) ? oA : oBn;
     const uintptr_t abase = (uintptr_t)d.base;
-    uintptr_t p16 = abase + (size_t)o16 * 256 + (nb + (size_t)Dp + (l == 1 ? 0 : 1)) * 16;
-    uintptr_t p4 = abase + (size_t)d.o_PP * 256 + (nb + (size_t)Dp + 1) * 4;
+    uintptr_t p16, p4;
+    if constexpr (kEntry) {
+        arena_nodes_at(d, (unsigned)apk & 0xffffu, (unsigned)apk >> 16);  // (for the reads off the in-sequence path)
+        const unsigned oA8 = oA8_of(), c8 = c8_of();
+        const unsigned k16 = (l == 0) ? kNodeSpanC : (l == 2) ? 0u : kNodeSpanBn;  // the lane's array, in units of c
+        const unsigned nd = (unsigned)t * (unsigned)P + (unsigned)Dp;
+        p16 = abase + (oA8 + k16 * c8 + (nd + (l == 1 ? 0u : 1u)) * 16);
+        p4 = abase + (oA8 + kNodeSpanPP * c8 + (nd + 1) * 4);
+    } else {
+        arena();
+        unsigned oA = d.o_A, oBn = d.o_Bn, oC = d.o_C;
+        asm volatile("" : "+s"(oA), "+s"(oBn), "+s"(oC));  // (values, not fields: no table in scratch)
+        const unsigned o16 = (l == 0) ? oC : (l == 2) ? oA : oBn;
+        p16 = abase + (size_t)o16 * 256 + (nb + (size_t)Dp + (l == 1 ? 0 : 1)) * 16;
+        p4 = abase + (size_t)d.o_PP * 256 + (nb + (size_t)Dp + 1) * 4;
+    }
     asm volatile("" : "+v"(p16), "+v"(p4));
     asm volatile("s_waitcnt lgkmcnt(0)"
                  : "+s"(hv), "+s"(kv), "+s"(r_i), "+s"(v_i)
@@ -3875,7 +4058,7 @@ __global__ __launch_bounds__(W4 ? 256 : 192) void k_chain3(char *base, const flo
     // one word per level below the root (its first level is forced while it has one visit): they
     // land while the distribution is built.  The exact case re-reads them after the barrier.
     constexpr int kK0 = (int)((offsetof(ChainIO, k) - offsetof(ChainIO, idx_x)) / 4);  // ChainK's first dword in kv
-    static_assert(kK0 == 6 && offsetof(ChainK, o_sq) == 32, "wave 0's argument line");
+    static_assert(kK0 == 6 && offsetof(ChainK, o_sq) == 32 && offsetof(ChainK, discount) == 36, "wave 0's argument line");
     const int omri = kv[kK0], gW = kv[kK0 + 1];
     d.o_R = (unsigned)kv[kK0 + 2];
     d.o_err = (unsigned)kv[kK0 + 3];
@@ -3884,6 +4067,7 @@ __global__ __launch_bounds__(W4 ? 256 : 192) void k_chain3(char *base, const flo
     const float gdelta = i2f(kv[kK0 + 6]);
     d.o_pb = (unsigned)kv[kK0 + 7];
     d.o_sq = (unsigned)kv[kK0 + 8];
+    const float discount = i2f(kEntry ? kv[kK0 + 9] : apk);
     const unsigned *Rt = d.R() + (size_t)t * gW;
     const int dA = (A >= 2) ? 2 : 0;
     const int words_fast = SEL ? (hv[2] + 1) - ((root_vis0 + 1 <= 1) ? 1 : 0) : 0;
@@ -3914,7 +4098,7 @@ __global__ __launch_bounds__(W4 ? 256 : 192) void k_chain3(char *base, const flo
     }
     const int D = h.D;
     if (D != Dp || h.tot != D + 1 || h.leaf != D) {
-        if (D + 1 > P || h.tot != D + 1 || h.leaf != D) {  // not a chain: refuse
+        if (no_chain(D, P, h.tot, h.leaf)) {  // refuse
             if (l == 0) {
                 if (SEL) {
                     idx_x[t] = 0;
@@ -6589,6 +6773,7 @@ struct mz_batch {
     int chain_nc = -1;         // k_chain node class for K = 1 trees (-1: k_step for every launch)
     int chain3_nc = 0;         // k_chain3 node class (64 .. 1024) for K = 1 trees, 0: k_chain / k_step
     bool chain3_w4 = false;    // k_chain3 with the draw wave (four waves; mz_create)
+    unsigned chain3_apk = 0;   // k_chain3's packed node-array offsets (arena_pack; mz_create)
     ChainK chain_k{};          // k_chain3's copy of the Params fields its waves read (mz_create)
     bool prep1 = false;        // mz_prepare / mz_prepare_select launch k_prepare1 (mz_create)
     Prep1IO prep1_io{};        // its argument line but for the call's own fields (mz_create)
@@ -6889,6 +7074,10 @@ struct ArenaPlan {
         req.push_back({&off, nullptr, total});
         total += span(count * sizeof(T));
     }
+    void dev_units(unsigned &off, size_t units) {  // a span given in 256-byte units (arena_nodes' node arrays)
+        req.push_back({&off, nullptr, total});
+        total += units * 256;
+    }
     template <typename T>
     void ptr(T **p, size_t count) {
         req.push_back({nullptr, (void **)p, total});
@@ -6955,19 +7144,24 @@ template <int NC, bool SEL, int ROW, bool W4>
 void launch_chain3_row(mz_batch *b, const StepArgs &a) {
     const Geo &g = b->geo;
     const Dev &dv = b->dev;
-    // (the first 14 argument dwords, through the discount, arrive preloaded in SGPRs)
-    const ChainIO io{a.pool, a.pool_stride, a.row_bytes, a.gather_out, b->chain_k.one_minus_rho, b->chain_k.o_stats,
+    // (the first 14 argument dwords, through the packed node-array offsets, arrive preloaded in SGPRs;
+    // the discount rides in wave 0's argument line, where wave 1 fetches it too)
+    ChainIO io{a.pool, a.pool_stride, a.row_bytes, a.gather_out, b->chain_k.one_minus_rho, b->chain_k.o_stats,
                      {0, 0, 0, 0, 0, 0}, a.idx_x, a.idy, a.act, b->chain_k};
+    io.k.discount = a.discount;
     // ROW 1, 2: the row size (16-byte units, <= 1024) rides in the preloaded ppk, the leaf's slot in
     // the first argument past the preloaded ones
     const bool pre = ROW == 1 || ROW == 2;
+    // ROW 2 keeps the earlier entry: its 14th dword is the discount, its offsets come from the geometry
+    int d14 = (int)b->chain3_apk;
+    if (ROW == 2) memcpy(&d14, &a.discount, sizeof d14);
     const char *src_slot = pre ? a.pool + (long long)a.hsx * a.pool_stride : nullptr;
     const int rb16 = pre ? (int)(a.row_bytes / 16) : 0;
     hipLaunchKernelGGL((k_chain3<NC, SEL, ROW, W4>), dim3(g.B), dim3((W4 ? 4 : 3) * kWave),
                        chain3_lds_bytes(NC) + (ROW == 2 ? 16 * 16 * kWave : 0), b->stream, (char *)dv.base, a.policy,
                        a.beta, a.reward, a.value, g.P | (g.PS << 10) | (rb16 << 20),
-                       (int)((unsigned)g.B | ((unsigned)g.A << 24) | ((unsigned)b->fast_ok << 31)), a.hsx, a.discount,
-                       src_slot, io);
+                       (int)((unsigned)g.B | ((unsigned)g.A << 24) | ((unsigned)b->fast_ok << 31)), a.hsx,
+                       d14, src_slot, io);
 }
 // the row class of a launch (k_chain3's ROW)
 int chain3_row(const StepArgs &a, bool sel) {
@@ -7545,12 +7739,15 @@ int mz_create(int B, int N, int A, int K, int S, float delta_lb, uint32_t seed, 
         plan.ptr(&b->prm, 1);
         plan.dev<TreeHdr>(d.o_hdr, (size_t)B);
         plan.dev<float>(d.o_lp, (size_t)b->PS + 1 + kWave);
-        plan.dev<int4>(d.o_A, nodes);
-        plan.dev<int>(d.o_Par, nodes);
-        plan.dev<int4>(d.o_Bn, nodes);
-        plan.dev<float>(d.o_Q, nodes);
-        plan.dev<float>(d.o_PP, nodes);
-        plan.dev<float4>(d.o_C, nodes);
+        // the node arrays, in multiples of the 4-byte arrays' span (arena_nodes)
+        const size_t cu = arena_unit((unsigned)nodes);
+        assert(cu * 256 == ArenaPlan::span(4 * nodes) && 4 * cu * 256 >= ArenaPlan::span(16 * nodes));
+        plan.dev_units(d.o_A, 4 * cu);
+        plan.dev_units(d.o_Par, cu);
+        plan.dev_units(d.o_Bn, 4 * cu);
+        plan.dev_units(d.o_Q, cu);
+        plan.dev_units(d.o_PP, cu);
+        plan.dev_units(d.o_C, 4 * cu);
         plan.dev<long long>(d.o_stats, (size_t)B * MZ_S_COUNT);
         plan.dev<int>(d.o_err, 1);
         plan.dev<unsigned>(d.o_seed, 1);
@@ -7565,7 +7762,7 @@ int mz_create(int B, int N, int A, int K, int S, float delta_lb, uint32_t seed, 
                         ArenaPlan::span(8 * ((size_t)b->PS + kWave));
         b->mem_values = ArenaPlan::span(8 * nodes * b->E);
         b->mem_stream = ArenaPlan::span(4 * (size_t)B * b->W);
-        b->mem_nodes = 4 * ArenaPlan::span(16 * nodes) + 3 * ArenaPlan::span(4 * nodes);
+        b->mem_nodes = (size_t)kNodeSpanEnd * cu * 256 + ArenaPlan::span(16 * nodes);  // (o_A .. o_C, and o_D)
         plan.ptr(&b->sel_dev, (size_t)B * (2 + N));
         plan.ptr(&b->in_dev, (size_t)B * (2 + 3 * (size_t)N * A));
         b->rb_words = (size_t)2 * B + 2 * (size_t)B * N * A + (size_t)MZ_F_COUNT * B * b->Wd * N;
@@ -7592,8 +7789,18 @@ int mz_create(int B, int N, int A, int K, int S, float delta_lb, uint32_t seed, 
     }
     // k_chain3 takes P and PS in 10 bits each (its pools have <= 256 nodes)
     // (pools above 256 nodes keep k_chain: wave 1 holds the chain's records in registers, 8 per 64 nodes)
-    if (b->chain_nc > 0 && b->chain_nc <= 256 && b->P < 1024 && b->PS < 1024 && !getenv_flag("MZ_CHAIN_V2"))
+    // and the node arrays' offset o_A and unit c in 16 bits each (arena_pack: up to some 16,000 trees of
+    // 256 nodes); a handle past that range keeps k_chain, which computes its offsets from the geometry --
+    // the route MZ_CHAIN_V2 forces at any size
+    const unsigned node_unit = arena_unit((unsigned)nodes);
+    if (b->chain_nc > 0 && b->chain_nc <= 256 && b->P < 1024 && b->PS < 1024 && arena_packs(d.o_A, node_unit) &&
+        !getenv_flag("MZ_CHAIN_V2")) {
         b->chain3_nc = b->chain_nc;
+        b->chain3_apk = arena_pack(d.o_A, node_unit);
+        // (k_chain3 addresses the records as the arena base plus a 32-bit byte offset)
+        assert(((unsigned long long)d.o_A + (unsigned long long)kNodeSpanEnd * node_unit) * 256 < (1ull << 32));
+        assert(d.o_stats == d.o_A + kNodeSpanEnd * node_unit);
+    }
     // the draw wave: in the 64-node class (in the longer chains of the larger classes wave 1 ends
     // last, and the start barrier holds it until wave 0 arrives: 27m K = 1 measured 2.6 % slower
     // with it) and while the workgroups fit one per CU (every wave of a workgroup on a SIMD of its
