@@ -57,6 +57,21 @@ int mz_reseed(mz_batch *b, uint32_t random_seed);
 int mz_set_active_roots(mz_batch *b, int n);
 int mz_get_active_roots(mz_batch *b, int *n);
 
+/* Root offset: tree i of the handle is seeded with random_seed * 2333 + root_offset + i (cnode.cpp:574
+ * for root root_offset + i of a larger batch), so that a handle searching rows [root_offset,
+ * root_offset + root_num) of a batch gives those rows of the whole batch's search.  mz_create sets it;
+ * mz_set_root_offset moves it, so that one handle and the graphs recorded on it follow a shard whose
+ * position in the batch changes from search to search (mazero_amd.mcts_sampled device_root_offset).
+ * The offset is a device word beside the seed: the call is one one-thread launch on the handle's
+ * stream, ordered with the handle's other work, and takes effect at the next mz_prepare /
+ * mz_prepare_select -- also one replayed from a captured graph, which reads the word like the seed.
+ * Like mz_reseed it is meant to be called outside a graph capture, before a replay.  It leaves the
+ * seed, the active-root count, the trees and a packed readback that is ready alone.
+ * 0 <= root_offset and root_offset + root_num <= INT32_MAX, else MZ_ERR_ARG.  mz_get_root_offset
+ * returns the host's copy of the value (no device call). */
+int mz_set_root_offset(mz_batch *b, int root_offset);
+int mz_get_root_offset(mz_batch *b, int *root_offset);
+
 /* Tell the handle that its trees were changed by work it did not enqueue itself -- the replay of
  * a captured graph of mz_* calls -- so that host-side readback caches are dropped.  (Captured
  * launches read the seed and every input from device memory, so a replay after mz_reseed and

@@ -114,6 +114,8 @@ DRIVER_SIGNATURES = {
     "mz_state_changed": (_i, [_p]),
     "mz_set_active_roots": (_i, [_p, _i]),
     "mz_get_active_roots": (_i, [_p, C.POINTER(_i)]),
+    "mz_set_root_offset": (_i, [_p, _i]),
+    "mz_get_root_offset": (_i, [_p, C.POINTER(_i)]),
     "mz_policy_glue": (_i, [_p, _p, _i, _i64, _i64, C.c_double, _p, _p]),
     "mz_root_glue": (_i, [_p, _p, _i, _i64, _i64, _p, _i64, _p, C.c_double, C.c_double, _p, _p, _p]),
     "mz_joint_action": (_i, [_p, _p, _i, _i, _i, _p, _i, _p, _p]),

@@ -101,7 +101,7 @@ struct Geo {
     int B, A, K, S, P, E, W, PS;
     int TT;         // pUCT table entries (PS*(PS+1)/2, padded to 4)
     int use_table;  // pUCT table staged in LDS (else pb/sq tables + double arithmetic)
-    int root_offset;
+    int root_offset;  // mz_create's value (host side: seed-table sizing); the kernels read Dev::seed()[1]
     unsigned seed;
     float one_minus_rho, delta;
     int reg_cap;  // value entries staged in LDS per back-propagation chunk
@@ -147,8 +147,17 @@ struct Dev {
     __host__ __device__ float *pb() const { return (float *)(base + (size_t)o_pb * 256); }  // [PS] logf((n + c2 + 1)/c2) + c1
     __host__ __device__ double *sq() const { return (double *)(base + (size_t)o_sq * 256); }  // [PS] sqrt(n)
     __host__ __device__ float *lp() const { return (float *)(base + (size_t)o_lp * 256); }  // [PS+1] lambda^d as a float chain
-    __host__ __device__ unsigned *seed() const { return (unsigned *)(base + (size_t)o_seed * 256); }  // [1] random_seed, read by k_prepare
+    __host__ __device__ unsigned *seed() const { return (unsigned *)(base + (size_t)o_seed * 256); }  // [2] {random_seed, root_offset}, read by k_prepare
 };
+
+// Tree t's std::mt19937 seed value, random_seed * 2333 + root_offset + t (cnode.cpp:574, the tree's
+// row in the unsharded batch).  Seed and root offset are device state (mz_reseed,
+// mz_set_root_offset), the first two words of a 256-byte block: one aligned 8-byte load carries both,
+// so the offset costs the seeding path no round trip of its own.
+__device__ __forceinline__ unsigned seed_value(const Dev &d, int t) {
+    const uint2 s = *(const uint2 *)d.seed();
+    return s.x * 2333u + s.y + (unsigned)t;
+}
 
 struct StepArgs {
     int hsx;
@@ -1433,7 +1442,7 @@ __global__ __launch_bounds__(256) void k_prepare(const Params *__restrict__ prm,
     // error also stays in its header, and every later kernel re-reports the errors of dead trees,
     // so an error raised by another block before this store is not lost.
     if (t == 0 && tid == 0) *d.err() = 0;
-    const unsigned seed_v = d.seed()[0] * 2333u + (unsigned)(g.root_offset + t);
+    const unsigned seed_v = seed_value(d, t);
     const unsigned *cp = prm->cp;
     if (cp && seed_v < prm->cp_n) {
         // the seeding chain from the checkpoints: lane j replays words 16j .. 16j + 15
@@ -1452,7 +1461,7 @@ __global__ __launch_bounds__(256) void k_prepare(const Params *__restrict__ prm,
         // std::mt19937::seed (sequential by definition) on the scalar unit: 4 SALU operations per
         // word, word i into lane i % 64 of VGPR i / 64 (mt_seed.inc, scripts/gen_mt_seed.py), then
         // ten LDS stores.  Replaces a compiler loop of ~6.5 instructions per word (10.4 us -> ...)
-        unsigned x = (unsigned)__builtin_amdgcn_readfirstlane((int)(d.seed()[0] * 2333u + (unsigned)(g.root_offset + t)));
+        unsigned x = (unsigned)__builtin_amdgcn_readfirstlane((int)seed_v);
         unsigned tt;
         int v0 = (int)x, v1 = 0, v2 = 0, v3 = 0, v4 = 0, v5 = 0, v6 = 0, v7 = 0, v8 = 0, v9 = 0;
         asm volatile(MZ_MT_SEED_ASM
@@ -6378,7 +6387,7 @@ struct Prep1IO {
     int *idx_x, *idy, *act;  // non-null: also the first selection (mz_prepare_select)
     const unsigned *cp;      // the seeding checkpoints (null: the chain) and their rows
     unsigned cp_n;
-    int W, root_offset;
+    int W, root_offset;  // (root_offset: mz_create's value, not read on the device -- seed_value)
     float eps;
     float one_minus_rho;
     unsigned o_R, o_D;
@@ -6527,7 +6536,7 @@ __global__ __launch_bounds__(kPrep1Waves *kWave) void k_prepare1(char *base, con
     // ======== waves 1 .. 4: the seeding (wave 1) and the twist ========
     const int k = (int)threadIdx.x - kWave;
     if (wv == 1) {
-        const unsigned seed_v = d.seed()[0] * 2333u + (unsigned)(io.root_offset + t);
+        const unsigned seed_v = seed_value(d, t);
         const unsigned *cp = io.cp;
         if (cp && seed_v < io.cp_n) {
             // the seeding chain from the checkpoints: lane j replays words 16j .. 16j + 15
@@ -6599,7 +6608,8 @@ __global__ __launch_bounds__(kPrep1Waves *kWave) void k_prepare1(char *base, con
 }
 
 // mz_create's device initialisation in one launch (instead of three copies and three memsets,
-// each a synchronous runtime call): the Params block, the seed word, the lambda powers (the float
+// each a synchronous runtime call): the Params block, the seed word and the root offset beside it
+// (mz_set_root_offset), the lambda powers (the float
 // chain lp[k] = lp[k - 1] * lam of utils.cpp:25-27, on one thread, in the order the host ran it),
 // zeroed tree headers, statistics and error word
 __global__ __launch_bounds__(256) void k_init(Params p, unsigned seed, float lam, int nlp, int hdr_words,
@@ -6608,7 +6618,8 @@ __global__ __launch_bounds__(256) void k_init(Params p, unsigned seed, float lam
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i == 0) {
         *(Params *)(void *)d.base = p;
-        *d.seed() = seed;
+        d.seed()[0] = seed;
+        d.seed()[1] = (unsigned)p.g.root_offset;
         *d.err() = 0;
         float *lp = d.lp();
         float v = 1.0f;
@@ -6741,6 +6752,7 @@ struct mz_batch {
     int B, N, A, K, S, P, E, W, PS, Wd;
     int NA;  // N * A: per-root policy / marginal entries
     int active = 0;  // roots [0, active) are what the getters and consumers see (mz_set_active_roots)
+    int root_offset = 0;  // host copy of Dev::seed()[1] (mz_create, mz_set_root_offset)
     int device;
     Geo geo;
     Dev dev;
@@ -7594,6 +7606,7 @@ int mz_create(int B, int N, int A, int K, int S, float delta_lb, uint32_t seed, 
     auto *b = new mz_batch;
     b->B = B;
     b->active = B;
+    b->root_offset = root_offset;
     b->N = N;
     b->A = A;
     b->NA = N * A;
@@ -8206,6 +8219,29 @@ int mz_set_active_roots(mz_batch *b, int n) {
 int mz_get_active_roots(mz_batch *b, int *n) {
     if (!b || !n) return fail(MZ_ERR_ARG, "mz_get_active_roots: null argument");
     *n = b->active;
+    return MZ_OK;
+}
+
+int mz_set_root_offset(mz_batch *b, int root_offset) {
+    if (!b) return fail(MZ_ERR_ARG, "null handle");
+    if (root_offset < 0) return fail(MZ_ERR_ARG, "root_offset must be >= 0");
+    if ((long long)root_offset + b->B > 0x7fffffffll) return fail(MZ_ERR_ARG, "root_offset + root_num > INT32_MAX");
+    OrderMark om{b};
+    int rc = ensure_device(b);
+    if (rc) return rc;
+    rc = flush_pending(b);
+    if (rc) return rc;
+    // (the trees and a ready packed readback still hold the last search: only the next prepare reads it)
+    b->root_offset = root_offset;
+    b->dirty = true;
+    hipLaunchKernelGGL(k_set_word, dim3(1), dim3(1), 0, b->stream, b->dev.seed() + 1, (unsigned)root_offset);
+    HIP_TRY(hipGetLastError());
+    return MZ_OK;
+}
+
+int mz_get_root_offset(mz_batch *b, int *root_offset) {
+    if (!b || !root_offset) return fail(MZ_ERR_ARG, "mz_get_root_offset: null argument");
+    *root_offset = b->root_offset;
     return MZ_OK;
 }
 

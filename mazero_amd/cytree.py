@@ -121,6 +121,7 @@ class Tree_batch:
             C.byref(self._h),
         )
         check(lib, rc, "Tree_batch")
+        self._root_offset = int(root_offset)
         self._keep = []  # host buffers that must outlive an enqueued call
         self._stream_ptr = None
         # device backends follow torch's current stream on every call (oracle libraries are host-only)
@@ -286,6 +287,31 @@ class Tree_batch:
             return self.root_num
         n = C.c_int(0)
         check(self._lib, self._get_active(self._h, C.byref(n)), "active_roots")
+        return int(n.value)
+
+    def set_root_offset(self, n: int):
+        """From the next prepare on, tree i is seeded as root n + i of a larger batch, as if the handle
+        had been created with root_offset=n (include/mzdriver.h mz_set_root_offset; product library
+        only).  One one-thread launch on the current stream, like reseed; call it outside a graph
+        capture."""
+        fn = getattr(self._lib, "mz_set_root_offset", None)
+        if fn is None:
+            raise RuntimeError("set_root_offset: this tree library has no mz_set_root_offset "
+                               "(include/mzdriver.h, product library only)")
+        self._sync_stream()
+        check(self._lib, fn(self._h, int(n)), "set_root_offset")
+        self._root_offset = int(n)
+
+    @property
+    def root_offset(self) -> int:
+        """The handle's root offset: the constructor's, or the last set_root_offset's.  Read from the
+        library's host copy (mz_get_root_offset, no device call); on a library without the entry point
+        it is the constructor's value."""
+        fn = getattr(self._lib, "mz_get_root_offset", None)
+        if fn is None:
+            return self._root_offset
+        n = C.c_int(0)
+        check(self._lib, fn(self._h, C.byref(n)), "root_offset")
         return int(n.value)
 
     def state_changed(self):

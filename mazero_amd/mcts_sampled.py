@@ -565,13 +565,24 @@ def _support_bounds(support) -> Tuple[int, int]:
     return lo, hi
 
 
+# the place of the root offset in the key of a handle whose offset is device state (device_root_offset)
+_DEVICE_OFFSET = "device_root_offset"
+
+
+def skip_search_draws(config, np_random, total: int) -> None:
+    """What one search of `total` roots draws from `np_random` before it launches anything: the
+    Dirichlet rows, then the tree seed (mcts_sampled.py:68,89)."""
+    np_random.dirichlet([config.root_dirichlet_alpha] * config.action_space_size, int(total))
+    np_random.choice(256)
+
+
 class SampledMCTS:
     """mcts_sampled.py:29-32.  `lib` selects the tree library (default: the MI355X product)."""
 
     def __init__(self, config, np_random: np.random.RandomState = None, *, lib=None, use_graph: bool = True,
                  root_shard: Tuple[int, int, int] = None, device_root: bool = True, wide_actions: bool = None,
                  fused_transforms: bool = None, wide_supports: bool = None, later_action_cache: bool = None,
-                 root_capacity: int = None):
+                 root_capacity: int = None, device_root_offset: bool = None):
         """`root_capacity` = C: every search of B <= C roots runs on the tree handle and the per-agent
         loops (static buffers, recorded graph) of the C-root geometry, so a batch that shrinks and grows
         (self-play searches only the environments still running, selfplay_worker.py:171-211; full-game
@@ -583,9 +594,20 @@ class SampledMCTS:
         results are rows [0, B) of the reference search over the padded C-row batch, and they equal the
         plain B-root search bit for bit whenever row i of the model's outputs and of the transforms does
         not depend on how many rows the batch has.  B > C raises ValueError.  None reads
-        `config.root_capacity` (off when the config has none).  Not with `root_shard`: a sharded rank's
-        tree i is seeded with its position in the whole batch, and that offset is a launch argument of the
-        prepare kernels baked into the recorded graph, so it cannot change per search.
+        `config.root_capacity` (off when the config has none).  Together with `root_shard` only under
+        `device_root_offset`.
+
+        `device_root_offset`: the tree handle's root offset follows the shard from search to search.  A
+        sharded rank's tree i is seeded with its position lo + i in the whole batch; that offset is a
+        device word beside the seed (Tree_batch.set_root_offset, include/mzdriver.h mz_set_root_offset),
+        which the prepare kernels read, so a recorded graph follows it.  With the flag the handle is keyed
+        without the offset: one handle and its recorded loops serve every shard position, the offset is
+        set next to the reseed whenever it differs from the handle's, `root_capacity=C` is accepted with
+        `root_shard=(lo, hi, total)` when hi - lo <= C, and an empty shard (lo == hi: a rank none of whose
+        environments still runs) is legal -- it searches nothing, and `skip_search` consumes what one
+        search draws from `np_random`, so every rank's generator stays in the same state.  None reads
+        `config.device_root_offset` (False when the config has none).  Off by default: the refusal of
+        `root_capacity` with `root_shard` is pinned by the test suite.
 
         `later_action_cache`: take the later agents' greedy actions of every simulation
         (mcts_sampled.py:136-147) from a per-node cache instead of a `model.prediction` pass on the
@@ -661,9 +683,16 @@ class SampledMCTS:
         self.later_action_cache = bool(later_action_cache)
         self.np_random = np.random if np_random is None else np_random
         self._lib = lib
+        if device_root_offset is None:
+            device_root_offset = getattr(config, "device_root_offset", False)
+        self.device_root_offset = bool(device_root_offset)
+        if self.device_root_offset and lib is not None and not hasattr(lib, "mz_set_root_offset"):
+            raise RuntimeError("device_root_offset needs a tree library with mz_set_root_offset "
+                               "(include/mzdriver.h, product library only)")
         if root_shard is not None:
             lo, hi, total = (int(x) for x in root_shard)
-            if not 0 <= lo < hi <= total:
+            # (an empty shard only where the handle follows the shard: skip_search)
+            if not (0 <= lo <= hi <= total and (lo < hi or self.device_root_offset)):
                 raise ValueError(f"bad root shard {root_shard}")
             root_shard = (lo, hi, total)
         self.root_shard = root_shard
@@ -673,10 +702,13 @@ class SampledMCTS:
             root_capacity = int(root_capacity)
             if root_capacity < 1:
                 raise ValueError(f"root_capacity must be >= 1, got {root_capacity}")
-            if root_shard is not None:
+            if root_shard is not None and not self.device_root_offset:
                 raise ValueError(f"root_capacity={root_capacity} with root_shard={root_shard}: a rank's trees "
                                  "are seeded from its root offset, a launch argument of the prepare kernels in "
                                  "the recorded graph, which cannot follow a varying root count")
+            if root_shard is not None and root_shard[1] - root_shard[0] > root_capacity:
+                raise ValueError(f"root_shard={root_shard} holds {root_shard[1] - root_shard[0]} roots, more than "
+                                 f"root_capacity={root_capacity}")
             if lib is not None and not hasattr(lib, "mz_set_active_roots"):
                 raise RuntimeError("root_capacity needs a tree library with mz_set_active_roots "
                                    "(include/mzdriver.h, product library only)")
@@ -773,6 +805,14 @@ class SampledMCTS:
             raise ValueError(f"batch of {B} roots but the root shard is [{lo}, {hi})")
         return draw(total)[lo:hi]
 
+    def skip_search(self) -> None:
+        """Consume from `np_random` exactly what one search consumes -- the Dirichlet rows of the whole
+        batch, then the tree seed (mcts_sampled.py:68,89) -- and launch nothing: the search of an empty
+        root shard (`device_root_offset`), which keeps this rank's generator in step with the others'."""
+        if self.root_shard is None or self.root_shard[0] != self.root_shard[1]:
+            raise ValueError(f"skip_search: root shard {self.root_shard} is not empty")
+        skip_search_draws(self.config, self.np_random, self.root_shard[2])
+
     def draw_root_uniforms(self, B: int) -> np.ndarray:
         """One double per root in root order, as B np_random.choice(n, p) calls draw them."""
         return np.asarray(self.draw_rows(lambda n: self.np_random.random(n), B), dtype=np.float64)
@@ -783,13 +823,15 @@ class SampledMCTS:
         # rewrite: a handle serves one pair only
         key = (threading.get_ident(), B, cfg.action_space_size, cfg.sampled_action_times, cfg.num_simulations,
                float(cfg.tree_value_stat_delta_lb), float(cfg.mcts_rho), float(cfg.mcts_lambda),
-               float(cfg.pb_c_base), float(cfg.pb_c_init), str(device), id(self._lib), self._root_offset())
+               float(cfg.pb_c_base), float(cfg.pb_c_init), str(device), id(self._lib),
+               _DEVICE_OFFSET if self.device_root_offset else self._root_offset())
         with _LOCK:
             tb = _TREES.get(key)
             if tb is None:
                 tb = Tree_batch(B, 1, cfg.action_space_size, cfg.sampled_action_times, cfg.num_simulations,
                                 cfg.tree_value_stat_delta_lb, int(seed), cfg.mcts_rho, cfg.mcts_lambda,
-                                root_offset=self._root_offset(), lib=self._lib)
+                                root_offset=0 if self.device_root_offset else self._root_offset(),
+                                lib=self._lib)
                 _TREES[key] = tb
                 while len(_TREES) > max(_MAX_TREES, 1):  # least recently used first, with its loops
                     _, old = _TREES.popitem(last=False)
@@ -797,6 +839,9 @@ class SampledMCTS:
             else:
                 _TREES.move_to_end(key)
                 tb.reseed(int(seed))
+            # (in the stream order of the reseed: the next prepare, eager or replayed, reads both words)
+            if self.device_root_offset and tb.root_offset != self._root_offset():
+                tb.set_root_offset(self._root_offset())
             return tb
 
     def _root_offset(self) -> int:
@@ -832,6 +877,8 @@ class SampledMCTS:
         Bc = B if self.root_capacity is None else self.root_capacity
         if B > Bc:
             raise ValueError(f"batch of {B} roots exceeds root_capacity={Bc}")
+        if B < 1:
+            raise ValueError("batch of 0 roots: an empty root shard searches nothing (skip_search)")
 
         raw = self.root_raw(network_output, cur, legal_actions_lst, add_noise) if self.device_root else None
         if raw is not None:

@@ -4,7 +4,9 @@ range of the batch's independent roots.
 Roots never interact (cnode.cpp:633-641, 663-669) and tree i is seeded with
 random_seed*2333 + i (cnode.cpp:574); creating each rank's batch with root_offset = its first
 global root therefore reproduces the unsharded batch bit-for-bit, with no collective on the data
-path.  The only collectives are the barrier / max-over-ranks of the benchmark clock and the
+path.  A handle's root offset can also be moved between searches (Tree_batch.set_root_offset), for
+a rank whose position changes: `active_shard` gives a rank's part of a varying active set.  The only
+collectives are the barrier / max-over-ranks of the benchmark clock and the
 periodic weight broadcast (mazero_amd.weights).
 """
 from __future__ import annotations
@@ -17,6 +19,26 @@ def shard_bounds(total_roots: int, world: int, rank: int) -> tuple[int, int]:
     q, r = divmod(total_roots, world)
     lo = rank * q + min(rank, r)
     return lo, lo + q + (1 if rank < r else 0)
+
+
+def active_shard(active, lo: int, hi: int) -> tuple[int, int, int]:
+    """(p_lo, p_hi, n): the positions in `active`, the sorted global list of the environments still
+    running, of those a rank owning [lo, hi) holds, and n = len(active).  Ownership is contiguous and
+    the list is sorted, so the positions are the contiguous range [p_lo, p_hi); p_lo is the number of
+    active environments on lower ranks, and a rank with none gets p_lo == p_hi.  The ranks' ranges
+    tile [0, n) in rank order: (p_lo, p_hi, n) is the rank's root shard of the search over the active
+    environments."""
+    p_lo = p_hi = n = 0
+    prev = None
+    for e in active:
+        e = int(e)
+        if prev is not None and e <= prev:
+            raise ValueError("active must be sorted and distinct")
+        prev = e
+        p_lo += e < lo
+        p_hi += e < hi
+        n += 1
+    return p_lo, p_hi, n
 
 
 def slice_inputs(inp, lo: int, hi: int):

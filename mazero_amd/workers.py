@@ -14,7 +14,11 @@ Here there is one process per GPU and one rank per process:
   global index, so rank r's decisions are rows [lo, hi) of the unsharded step, bit for bit;
 - the weights travel by one collective from the learner's rank (`weights.WeightBroadcaster`, RCCL
   over xGMI on MI355X; gloo on the CPU), with the reference's checkpoint-interval rule;
-- nothing crosses ranks during a search.
+- nothing crosses ranks during a search;
+- with `shard_active`, self-play ranks search only the environments still running: each rank takes
+  its part of the sorted global active list (`shard.active_shard`, `gather_active`) as the root shard
+  of the search over that list, on one tree handle whose root offset follows the shard on the device
+  (`SampledMCTS(..., device_root_offset=True)`).
 
 The environment, the replay buffer and the learner stay out of scope: `env` is a
 callable that yields a shard's observations and legal-action masks, and `learner` is an optional
@@ -32,7 +36,7 @@ import numpy as np
 import torch
 import torch.distributed as dist
 
-from .shard import shard_bounds
+from .shard import active_shard, shard_bounds
 
 
 def _rank_world(group=None):
@@ -63,11 +67,26 @@ def _device_reanalyze_decide(mcts, model, network_output, legal, policy_mask, de
     return reanalyze_policy_targets(mcts, model, network_output, legal, policy_mask, device)._asdict()
 
 
-def _default_mcts(config, np_random, root_shard, wide_actions=None, later_action_cache=None, root_capacity=None):
+def _default_mcts(config, np_random, root_shard, wide_actions=None, later_action_cache=None, root_capacity=None,
+                  device_root_offset=None):
     from .mcts_sampled import SampledMCTS
 
     return SampledMCTS(config, np_random, root_shard=root_shard, wide_actions=wide_actions,
-                       later_action_cache=later_action_cache, root_capacity=root_capacity)
+                       later_action_cache=later_action_cache, root_capacity=root_capacity,
+                       device_root_offset=device_root_offset)
+
+
+def gather_active(local_active, group=None) -> np.ndarray:
+    """The sorted global list of the environments still running, from each rank's own: an
+    all_gather_object of the ranks' running global indices, so that every rank holds the same `active`
+    for SelfPlayShard.step without a collective of the caller's.  Without a process group the local
+    list is the global one."""
+    local = [int(i) for i in np.asarray(local_active, dtype=np.int64).reshape(-1)]
+    if not (dist.is_available() and dist.is_initialized()) or dist.get_world_size(group) == 1:
+        return np.asarray(sorted(local), dtype=np.int64)
+    parts = [None] * dist.get_world_size(group)
+    dist.all_gather_object(parts, local, group=group)
+    return np.asarray(sorted(i for part in parts for i in part), dtype=np.int64)
 
 
 @dataclass
@@ -91,11 +110,18 @@ class _Shard:
     def __init__(self, model, config, total: int, *, seed: int, broadcaster=None, group=None, src: int = 0,
                  make_mcts: Optional[Callable] = None, device=None, rank: Optional[int] = None,
                  world: Optional[int] = None, wide_actions: Optional[bool] = None,
-                 later_action_cache: Optional[bool] = None, root_capacity: Optional[int] = None):
+                 later_action_cache: Optional[bool] = None, root_capacity: Optional[int] = None,
+                 shard_active: Optional[bool] = None):
         """`root_capacity` goes to the default search (SampledMCTS: every search of up to that many
-        roots on one tree handle and one set of recorded loops; None reads `config.root_capacity`).  It
-        needs world == 1, where the shard builds its search without a root shard (the whole batch is the
-        shard): SampledMCTS refuses it together with a root shard.
+        roots on one tree handle and one set of recorded loops; None reads `config.root_capacity`).
+        Without `shard_active` it needs world == 1, where the shard builds its search without a root
+        shard (the whole batch is the shard): SampledMCTS refuses it together with a root shard.
+        `shard_active`: SelfPlayShard.step(active=...) on any rank.  The rank searches the active
+        environments it owns as the root shard shard.active_shard(active, lo, hi) of the search over the
+        whole active list, on one tree handle of `root_capacity` roots (default: the rank's own hi - lo)
+        whose root offset follows the shard on the device (SampledMCTS device_root_offset).  None reads
+        `config.shard_active` (False when the config has none: the refusal of step(active=...) with
+        world > 1 is pinned by the test suite).
         `wide_actions` goes to the default search (SampledMCTS: action spaces up to 255 instead of
         64; None reads `config.wide_actions`), and so does `later_action_cache` (the later agents'
         greedy actions from a per-node cache; None reads `config.later_action_cache`); a `make_mcts` of
@@ -112,11 +138,18 @@ class _Shard:
         # the same generator state on every rank: sharded draws are sliced from whole-batch draws
         self.np_random = np.random.RandomState(seed)
         self.broadcaster, self.src, self.group = broadcaster, src, group
+        if shard_active is None:
+            shard_active = getattr(config, "shard_active", False)
+        self.shard_active = bool(shard_active)
         self.make_mcts = make_mcts or (lambda c, r, s: _default_mcts(c, r, s, wide_actions, later_action_cache,
                                                                      root_capacity))
         if root_capacity is None:
             root_capacity = getattr(config, "root_capacity", None)
         self.root_capacity = root_capacity
+        # step(active=...) under shard_active: the search of the rank's active environments
+        cap = (self.hi - self.lo) if root_capacity is None else int(root_capacity)
+        self.make_active_mcts = make_mcts or (lambda c, r, s: _default_mcts(c, r, s, wide_actions, later_action_cache,
+                                                                            cap, device_root_offset=True))
         self.device = device
         self.model_index = -1
         if broadcaster is not None and self.rank == src and broadcaster.model_index < 0:
@@ -174,11 +207,17 @@ class SelfPlayShard(_Shard):
         `active`: the sorted indices of the environments still running (selfplay_worker.py:171); `obs`,
         `legal` and `eps_uniforms` then hold those rows only and the step searches len(active) roots, as
         the reference does (:180-211).  The search is built without a root shard, so the per-root draws
-        are made for the active rows.  Single rank only: on a sharded rank tree i must be seeded with its
-        position in the whole active list, and the rank's root offset is a launch argument of the prepare
-        kernels baked into the recorded graph, so it cannot change per step."""
+        are made for the active rows.  Single rank only, unless the shard was built with `shard_active`.
+
+        With `shard_active`, on any rank: `active` is the global list (the same on every rank;
+        gather_active), `obs` / `legal` hold the rows of this rank's active environments only, and
+        `eps_uniforms` are whole-active-batch [N, len(active)] arrays, sliced here.  The rank's search is
+        the root shard shard.active_shard(active, lo, hi) of the search over the active list, so the
+        ranks' records, concatenated, are the single rank's record bit for bit.  A rank none of whose
+        environments runs calls neither the model nor the search: it draws from `np_random` what the
+        other ranks draw and returns a record of zero rows."""
         if active is not None:
-            if self.world > 1:
+            if self.world > 1 and not self.shard_active:
                 raise NotImplementedError(
                     "SelfPlayShard.step(active=...) with world > 1: tree i is seeded with its position in the "
                     "whole active list, so the rank's root offset would change per step, and that offset is a "
@@ -187,8 +226,19 @@ class SelfPlayShard(_Shard):
             if active.size < 1 or (np.diff(active) <= 0).any() or active[0] < 0 or active[-1] >= self.total:
                 raise ValueError(f"active must be sorted, distinct indices in [0, {self.total})")
         idx = self._sync()  # _update_model_before_step, selfplay_worker.py:176-177
+        if active is not None and self.shard_active:
+            if isinstance(eps_uniforms, str):  # ("torch": torch's global stream, consumed root by root)
+                raise NotImplementedError(f"eps_uniforms={eps_uniforms!r} with shard_active: pass the whole "
+                                          "active batch's uniforms as arrays")
+            p_lo, p_hi, n = active_shard(active, self.lo, self.hi)
+            if p_lo == p_hi:
+                return self._idle_step(t, idx, n, active)
+            if eps_uniforms is not None:
+                eps_uniforms = tuple(np.asarray(u)[:, p_lo:p_hi] for u in eps_uniforms)
         net_out = self._initial_inference(obs)
-        if active is not None:
+        if active is not None and self.shard_active:
+            mcts = self.make_active_mcts(self.config, self.np_random, (p_lo, p_hi, n))
+        elif active is not None:
             mcts = self.make_mcts(self.config, self.np_random, None)
         else:
             mcts = self.make_mcts(self.config, self.np_random, self._search_shard())  # :187
@@ -201,11 +251,25 @@ class SelfPlayShard(_Shard):
                           _to_np(d["root_value"]).reshape(-1), _to_np(d["count_entropy"]),
                           _to_np(d["visit_entropy"]), active)
 
+    def _idle_step(self, t: int, idx: int, n: int, active) -> StepRecord:
+        """A step in which none of this rank's environments runs: nothing is launched; `np_random`
+        moves as on every other rank -- per agent one search's draws (mcts_sampled.skip_search_draws),
+        then select_action's uniforms of the n active roots (draw_root_uniforms)."""
+        from .mcts_sampled import skip_search_draws
+
+        N = self.num_agents
+        for _ in range(N):
+            skip_search_draws(self.config, self.np_random, n)
+            self.np_random.random(n)
+        return StepRecord(t, idx, self.lo, np.zeros((0, N), np.int32), np.zeros(0, np.float64),
+                          np.zeros(0, np.float32), np.zeros((0, N), np.float64), np.zeros((0, N), np.float64), active)
+
     def run(self, env: Callable, steps: int, *, learner: Optional[Callable] = None, eps_uniforms: Callable = None,
             **step_kw) -> List[StepRecord]:
         """`steps` environment steps.  env(t, lo, hi) -> (obs, legal) for environments [lo, hi), or
         (obs, legal, active) with the rows of the environments `active` still running (see step; None:
-        all of them); learner(model, t) on the source rank after step t -> the trained-steps counter to
+        all of them; with `shard_active` the global list, with the rows of this rank's part of it);
+        learner(model, t) on the source rank after step t -> the trained-steps counter to
         publish (or None); eps_uniforms(t) -> whole-batch (u_eps, u_cat) or None, sliced to the active
         environments here."""
         out = []
