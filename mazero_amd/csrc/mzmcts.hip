@@ -848,8 +848,9 @@ __device__ __forceinline__ double cdf_terms(int A, const float *sw, double *sp, 
 // zeros and return finite values nobody reads (masked by l < A at every use).
 // Precondition: row_newbcast reads the source lane's register only if that lane is active, so
 // lanes 0..15 of the wave must be active, in wave-uniform control flow.  Holds at both call sites,
-// k_chain3's draw wave and wave 0's own draw when the hand-over runs out of polls: whole waves in
-// straight-line code behind uniform branches (the wave index, A, the slot's readfirstlane).
+// k_chain3's draw wave and wave 0's own draw (the predicate false, or a hand-over out of polls): whole
+// waves in straight-line code behind uniform branches (the wave index, A, the predicate's ballot,
+// the slot's readfirstlane).
 // Every other expansion keeps the LDS form (cdf_terms) or v_readlane (cdf_lane): routed through
 // this table, wave 0 of the three-wave k_chain3 and k_tree measured slower (they hide other work
 // behind the LDS waits; profiles/cdf_row/).
@@ -3518,7 +3519,22 @@ int chain3_lds_bytes(int nc) { return Chain3Layout<0>(nc).total; }
 // top bits: wave 2 issues the row's loads as soon as src_slot has landed, ahead of its scalar round.
 //
 // W4: a fourth wave (the draw wave) builds the expansion's distribution and draws the action from
-// launch start, beside wave 0's round 1 -- it needs only this launch's beta row and the header's two
+// launch start, beside wave 0's round 1.
+//
+// With a selection and the role-first entry (SEL, ROW != 2: kDS in the kernel) the draw wave stores
+// what it draws and the two waves never talk.  Both load the same header line, policy and beta rows,
+// reward, value and arguments and evaluate one predicate (draw_pred): no error, the chain in
+// sequence with a valid hot copy, and select_walk's fast case whatever the draw (every lane's prior
+// tame).  When it holds, the drawn action feeds five words only -- A[child].y (the prior),
+// Bn[child].y (the action), act[t], the header's leaf_y and D[child] under the root -- and the draw
+// wave stores them, the two records whole; wave 0 writes everything else and ends without an action.
+// When it does not hold, the draw wave returns without a store and wave 0 draws itself in registers
+// (cdf_short, cdf_lane past 16 actions).  No LDS slot, no start barrier, no poll: waves 1 and 2
+// never wait for another wave.  -DMZ_CHAIN3_DRAW_STORES=0 makes the predicate false everywhere (the
+// tests' second build).
+//
+// The fused readback (SEL = false) and the 16 KiB row class (ROW = 2) keep the hand-over: there the
+// draw wave needs only this launch's beta row and the header's two
 // engine words, both addressed from the preloaded arguments.  It hands the action to wave 0 through
 // one LDS dword (kDrawSlot of the oX region: bit 31 set, the action below it, one store).  LDS is not
 // cleared between workgroups, so wave 0 clears the slot and one s_barrier, taken by all four waves
@@ -3531,6 +3547,9 @@ constexpr int kDrawSlot = 4;  // dword of the oX region (0, 1: min / max; stamps
 #define MZ_CHAIN3_POLLS 128  // ~100 cycles each: several times the draw wave's ~2,000 cycles
 #endif
 constexpr int kDrawPolls = MZ_CHAIN3_POLLS;
+#ifndef MZ_CHAIN3_DRAW_STORES
+#define MZ_CHAIN3_DRAW_STORES 1  // 0: draw_pred false everywhere (wave 0 draws, the draw wave stores nothing)
+#endif
 __device__ __forceinline__ void start_barrier() { asm volatile("s_barrier" ::: "memory"); }
 // the slot's accesses: volatile (every poll reads LDS again) and typed as LDS (a volatile access
 // through a generic pointer is a flat one, which also waits for the wave's global stores)
@@ -3564,6 +3583,8 @@ __global__ __launch_bounds__(W4 ? 256 : 192) void k_chain3(char *base, const flo
     // with the role-first entry 27m K = 1 measured 3.2 % slower whatever the order of the role tests
     // (profiles/chain3_entry).
     constexpr bool kEntry = ROW != 2;
+    // the draw wave stores what it draws (above); the other four-wave instantiations hand over
+    constexpr bool kDS = W4 && SEL && kEntry, kHand = W4 && !kDS;
     // (stamped builds: every role's phases count from its wave's first instruction)
     unsigned long long ts[8] = {0};
     stamp(ts, 0);
@@ -3627,11 +3648,89 @@ __global__ __launch_bounds__(W4 ? 256 : 192) void k_chain3(char *base, const flo
     auto no_chain = [&](int D, int P, int toth, int leafh) {
         return (kEntry ? (unsigned)D >= (unsigned)P : D + 1 > P) || toth != D + 1 || leafh != D;
     };
+    // (kDS) "the launch is fast whatever the draw", the one predicate of wave 0 and the draw wave:
+    // both evaluate it from the same loaded words (hv: the header line; wild: the lane's prior is
+    // not tame).  It implies err == 0, tame == 1 and select_walk's fast case for every action.
+    auto draw_pred = [&](const int16v &hv, int omri, int disc_i, int r_i, int v_i, bool wild) {
+        if (!MZ_CHAIN3_DRAW_STORES) return false;
+        // Branch-free, a few dozen scalar instructions on both waves' critical paths: every equality
+        // is one xor into `ne`, every bound one difference whose sign bit goes into `neg` (32-bit
+        // wrap-around only ever fails a bound that held, and then wave 0 draws: the predicate is
+        // sufficient, not necessary).  Floats by their bits: |x| <= c is (bits & 0x7fffffff) <=
+        // bits(c), false for NaN; value_lim(1, omr) == 1 when omr's bits are at most 1.0f's (or omr
+        // is at most -1.0: the wrapped difference).
+        const unsigned P = (unsigned)P_of(), PS = (unsigned)PS_of(), toth = (unsigned)hv[1], D = (unsigned)hv[2];
+        const unsigned kAbs = 0x7fffffffu, kTame = 0x7149f2cau /* 1e30f */, kOne = 0x3f800000u /* 1.0f */;
+        // no error, the chain in sequence (D == hsx, tot, leaf), the hot copy (root_vis, leaf_y) valid
+        const unsigned ne = (unsigned)hv[3] | (D ^ (unsigned)hsx) | (toth ^ (D + 1u)) | ((unsigned)hv[7] ^ D) |
+                            ((unsigned)hv[11] ^ toth);
+        const unsigned va = (unsigned)v_i & kAbs, ra = (unsigned)r_i & kAbs;
+        unsigned neg = D | (P - 2u - D) | (PS - 2u - D);           // 0 <= D, no err1 (pool) / errp (path)
+        neg |= PS - 1u - (unsigned)hv[9];                          // no table error (root_vis < PS)
+        neg |= kOne - (unsigned)omri;                              // no err1 (value set)
+        neg |= ~(unsigned)bak | ((unsigned)hv[8] - 1u);            // fast_ok, h.tame (0 or 1)
+        neg |= kTame - (va > ra ? va : ra);                        // v_in, r_in tame
+        neg |= kOne - ((unsigned)disc_i & kAbs);                   // |discount| <= 1
+        return (ne | (neg >> 31)) == 0 && ballot(wild) == 0;
+    };
 
     auto wave3 = [&]() {
-        if constexpr (W4) {
+        if constexpr (kDS) {
+            // ======== wave 3: the expansion's distribution and draw (cnode.cpp:224-295), and the
+            // stores of the words the draw feeds ========
+            // Round 1 as wave 0's: the header line, this launch's rows and scalars, and of wave 0's
+            // argument line what the predicate and the stores need.  When the predicate fails wave 0
+            // draws and stores; this wave returns.
+            if (!MZ_CHAIN3_DRAW_STORES) return;
+            const int A = A_of(), P = P_of();
+            constexpr int kK = kIo + (int)offsetof(ChainIO, k);
+            const gchar *hb = hb_of();
+            int16v hv = sload16<kHdr8>(hb);
+            int2v actp = sload2<kIo + (int)offsetof(ChainIO, act)>(ka);
+            int omri = sload1<kK + (int)offsetof(ChainK, one_minus_rho)>(ka);
+            int oDi = sload1<kK + (int)offsetof(ChainK, o_D)>(ka);
+            int g_i = sload1<kK + (int)offsetof(ChainK, discount)>(ka);
+            int r_i = sload1(in_t(reward)), v_i = sload1(in_t(value));
+            const float pol = in_row(policy, A), bet = in_row(beta, A);
+            // lane 2 the child's A, lane 3 the child's Bn (whole records, as wave 0's lanes store them
+            // when it draws); the child of an in-sequence launch is hsx + 1 (clamped here: the
+            // predicate fails when hsx is out of range)
+            const unsigned nd1 = (unsigned)t * (unsigned)P + (unsigned)Dp_of(P) + 1;
+            const uintptr_t abase = (uintptr_t)d.base;
+            uintptr_t p16 = abase + (oA8_of() + (l == 2 ? 0u : kNodeSpanBn) * c8_of() + nd1 * 16);
+            asm volatile("" : "+v"(p16));
+            asm volatile("s_waitcnt lgkmcnt(0)"
+                         : "+s"(hv), "+s"(actp), "+s"(omri), "+s"(oDi), "+s"(g_i), "+s"(r_i), "+s"(v_i)
+                         :
+                         : "memory");
+            const float prior_l = pol * 1.0f / bet;  // (betahat_prob = 1, as wave 0's priors())
+            if (!draw_pred(hv, omri, g_i, r_i, v_i, !tame_prior(prior_l))) return;
+            int a = 0;
+            if (A >= 2) {
+                const double cp = (A <= 16) ? cdf_short(A, (l < A) ? bet : 0.f)
+                                            : cdf_bcast(bet, A, (float *)(smem + L.oW), (double *)(smem + L.oP));
+                const double u = draw_u((unsigned)hv[12], (unsigned)hv[13]);
+                a = __popcll(ballot(l < A && cp < u));  // lower_bound
+            }
+            a = uni(a);
+            const int by = pack_y(0, a, -1);
+            const float prior = rlf(prior_l, a);
+            const int4v d16 = {0, l == 2 ? f2i(prior) : by, 0, l == 3 ? -1 : 0};
+            if (l == 2 || l == 3) st_lane16(p16, d16);
+            if (l == 3) st_lane4((uintptr_t)u64_of(actp[0], actp[1]) + ((unsigned)t << 2), a);
+            if (hv[2] == 0) {  // (readbacks: root children)
+                const float pol_a = rlf(pol, a), bet_a = rlf(bet, a);
+                d.o_D = (unsigned)oDi;
+                if (l == 0) d.D()[(size_t)nd1] = make_float4(pol_a, bet_a, 1.0f, 0.f);
+            }
+            if (l == 0) {
+                hdr_of(hb)->leaf_y = by;
+                if (MZ_STAMPS) sXl[3] = (long long)(__builtin_amdgcn_s_memtime() - ts[0]);  // this wave's end
+            }
+            wait_lds();
+        } else if constexpr (W4) {
             const int A = A_of();
-            // ======== wave 3: the expansion's distribution and draw (cnode.cpp:224-295) ========
+            // ======== wave 3 (the hand-over): the expansion's distribution and draw (cnode.cpp:224-295) ========
             // Straight-line code: this launch's beta row and the header's two engine words, the
             // start barrier while they are in flight, the distribution, one LDS store.  No header
             // check (on a dead or out-of-chain tree wave 0 returns before it reads the slot; the
@@ -3725,7 +3824,7 @@ __global__ __launch_bounds__(W4 ? 256 : 192) void k_chain3(char *base, const flo
         load(Dp);  // (one round: every address follows from the preloaded arguments)
         if constexpr (kEntry) asm volatile("s_waitcnt lgkmcnt(0)" : "+s"(hv), "+s"(r_i), "+s"(v_i), "+s"(g_i)::"memory");
         else asm volatile("s_waitcnt lgkmcnt(0)" : "+s"(hv), "+s"(r_i), "+s"(v_i)::"memory");
-        if constexpr (W4) start_barrier();  // (every wave, before any return: wave 0's slot clear)
+        if constexpr (kHand) start_barrier();  // (every wave, before any return: wave 0's slot clear)
         const float r_in = i2f(r_i), v_in = i2f(v_i);
         const int herr = hv[3], D = hv[2], toth = hv[1], leafh = hv[7];
         if (herr) return;  // (wave 0 reports; no wave takes the barrier on the error paths)
@@ -3869,7 +3968,7 @@ __global__ __launch_bounds__(W4 ? 256 : 192) void k_chain3(char *base, const flo
         // (every wave takes the start barrier before any return: wave 0's slot clear.  Here ahead of
         // the wait: this wave's round 1 is two dependent scalar round trips with ROW 1, 2, and the
         // other waves would wait at the barrier for the second)
-        if constexpr (W4) start_barrier();
+        if constexpr (kHand) start_barrier();
         asm volatile("s_waitcnt lgkmcnt(0)" : "+s"(io8), "+s"(hv) : : "memory");
         const int omri = io8[8], osti = io8[9];
         const int P = P_of(), PS = PS_of();
@@ -4024,7 +4123,7 @@ __global__ __launch_bounds__(W4 ? 256 : 192) void k_chain3(char *base, const flo
         pol = policy[(size_t)t * A + (l < A ? l : 0)];
         bet = beta[(size_t)t * A + (l < A ? l : 0)];
     }
-    if constexpr (W4) {  // the hand-over slot, cleared ahead of the start barrier (round 1's wait covers the store)
+    if constexpr (kHand) {  // the hand-over slot, cleared ahead of the start barrier (round 1's wait covers the store)
         if (l == 0) draw_slot_set(sXi, 0);
     }
     // This launch's record stores, one per lane, from addresses held in registers: lane 0 the child's
@@ -4054,7 +4153,7 @@ __global__ __launch_bounds__(W4 ? 256 : 192) void k_chain3(char *base, const flo
                  : "+s"(hv), "+s"(kv), "+s"(r_i), "+s"(v_i)
                  :
                  : "memory");
-    if constexpr (W4) start_barrier();  // (every wave, before any return: the slot is clear from here)
+    if constexpr (kHand) start_barrier();  // (every wave, before any return: the slot is clear from here)
     // The root's visit count and the leaf's Bn.y: the header's copy when the previous launch left a
     // valid one (k_prepare, k_chain3), else the records (one more round trip: the first fused launch
     // after a host-path step, or after any other kernel wrote the header)
@@ -4170,8 +4269,26 @@ __global__ __launch_bounds__(W4 ? 256 : 192) void k_chain3(char *base, const flo
         wild_l = tame_prior(prior_l) ? 0 : 1;
         asm volatile("" : "+v"(prior_l), "+v"(wild_l));
     };
-    int fell = 0;  // (stamped builds: hand-overs that ran out of polls)
-    if constexpr (W4) {
+    int fell = 0;  // (stamped builds: hand-overs that ran out of polls; kDS: launches this wave drew)
+    bool ds = false;  // (kDS) the draw wave stores the drawn words: this wave reads no action
+    if constexpr (kDS) {
+        priors();
+        early();
+        stamp(ts, 7);
+        // (D == hsx in range, so the early stores' addresses above are this predicate's)
+        ds = draw_pred(hv, omri, kv[kK0 + 9], r_i, v_i, wild_l != 0);
+        if (!ds) {
+            // this wave draws itself, in registers, from the same words in the same order
+            fell = 1;
+            if (A >= 2) {
+                const float w = (l < A) ? bet : 0.f;
+                const double cp = (A <= 16) ? cdf_short(A, w) : cdf_lane((double)w, A);
+                const double u = draw_u(h.nxt[0], h.nxt[1]);
+                a = __popcll(ballot(l < A && cp < u));  // lower_bound
+            }
+        }
+        if (A >= 2) cursor += 2;
+    } else if constexpr (W4) {
         // the draw wave's action: a bounded poll of the hand-over slot (an LDS read, a readfirstlane
         // and a scalar test each)
         priors();
@@ -4217,6 +4334,33 @@ __global__ __launch_bounds__(W4 ? 256 : 192) void k_chain3(char *base, const flo
     }
     a = uni(a);
     stamp(ts, 2);
+    if constexpr (kDS && !MZ_STAMPS) {
+        // ---- the draw wave stores the drawn words: the rest of the header and the end ----
+        // The predicate gives err == 0, tame == 1 and select_walk's fast case (one word per level but
+        // the forced first one; no barrier).  The wait is counted: behind the engine words' load
+        // this wave has issued early()'s two stores and nothing else (both run under the predicate:
+        // err1 == 0, so lanes 0 and 1 store), and loads and stores retire in issue order -- no wait
+        // for the stores' own round trip, which the poll of the hand-over used to cover.
+        // (stamped builds take the general path below: wave 1's stamps come through the barrier)
+        if (ds) {
+            unsigned nxt_ds = (wi >= 0 && wi < gW) ? w_fast : 0u;  // (cursor + words + l == wi)
+            asm volatile("s_waitcnt vmcnt(2)" : "+v"(nxt_ds) : : "memory");
+            if (l < kNxt) hp->nxt[l] = nxt_ds;
+            if (l == 0) {
+                hp->cursor = cursor + Ds - ((root_vis0 + 1 <= 1) ? 1 : 0);
+                hp->tot = c + 1;
+                hp->D = Ds;
+                hp->err = 0;
+                hp->mm_cnt = D;  // (mm_min / mm_max: wave 1; leaf_y: the draw wave)
+                hp->tame = 1;
+                hp->leaf = c;
+                hp->root_vis = root_vis0 + 1;
+                hp->hot_tag = c + 1;
+            }
+            span_close(hsx, rt0);
+            return;
+        }
+    }
     // ---- after the draw: the drawn lane's prior, the words it feeds, their stores ----
     const float prior = rlf(prior_l, a);
     const bool wild = rl(wild_l, a) != 0;
@@ -4231,9 +4375,10 @@ __global__ __launch_bounds__(W4 ? 256 : 192) void k_chain3(char *base, const flo
     if (fast && l < kNxt) hp->nxt[l] = nxt_fast;
     // (sel_lane: two v_cndmask; the compiler makes branches of the selects)
     d16.y = f2i(sel_lane(sel_lane(i2f(d16.y), prior, 1ull << 2), i2f(pack_y(0, a, -1)), 1ull << 3));
-    if ((l == 2 || l == 3) && !err1) st_lane16(p16, d16);
-    if (SEL && l == 3) st_lane4(p4, any_err ? 0 : a);
-    if (!err1 && leaf == 0) {  // (readbacks: root children)
+    // (ds: the draw wave stores the drawn words -- the child's A and Bn, act[t], D[child], leaf_y below)
+    if ((l == 2 || l == 3) && !err1 && !ds) st_lane16(p16, d16);
+    if (SEL && l == 3 && !ds) st_lane4(p4, any_err ? 0 : a);
+    if (!err1 && leaf == 0 && !ds) {  // (readbacks: root children)
         const float pol_a = rlf(pol, a), bet_a = rlf(bet, a);
         if (l == 0) d.D()[nb + c] = make_float4(pol_a, bet_a, bh, 0.f);
     }
@@ -4298,7 +4443,7 @@ __global__ __launch_bounds__(W4 ? 256 : 192) void k_chain3(char *base, const flo
         // the hot copy for the next launch: wave 1 adds this back-propagation's visit to the root, and
         // the new leaf is the child created above (its Bn.y as stored there)
         hp->root_vis = root_vis0 + 1;
-        hp->leaf_y = pack_y(0, a, -1);
+        if (!ds) hp->leaf_y = pack_y(0, a, -1);
         hp->hot_tag = (err || !SEL) ? 0 : c + 1;
     }
     if constexpr (!SEL) {
@@ -4342,7 +4487,7 @@ __global__ __launch_bounds__(W4 ? 256 : 192) void k_chain3(char *base, const flo
             case MZ_S_CYC_W1_ROUND1: add = sXl[2]; break;                    // wave 1: round 1
             // the draw wave (W4): its end after launch start, wave 0's wait at the hand-over slot
             // (part of the distribution + draw span above), hand-overs that ran out of polls (a count)
-            case MZ_S_CYC_EXP_DRAW: add = W4 ? sXl[3] : 0; break;
+            case MZ_S_CYC_EXP_DRAW: add = (kDS ? ds : W4) ? sXl[3] : 0; break;  // (kDS: stamped when it stored)
             case MZ_S_CYC_BAK_WAIT: add = W4 ? (long long)(ts[2] - ts[7]) : 0; break;
             case MZ_S_CYC_EXP_NODES: add = fell; break;
             case MZ_S_STAMPED: add = 1; break;
