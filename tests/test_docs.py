@@ -102,3 +102,36 @@ def test_design_table_is_the_committed_reconciliation():
     for k, (msims, us) in rows.items():
         assert abs(msims - rec[k]["value"] / 1e6) < 0.05, k
         assert abs(us - rec[k]["avg_launch_us"]) < 0.006, k
+
+
+def test_source_map_is_the_sources():
+    """DESIGN §3's "Source map" against mazero_amd/csrc/: every .inc part is included by exactly one
+    `#include "..."` line of a .hip or .inc file of the folder, the table lists exactly the folder's
+    .hip, .inc and .h files, and every kernel a row names is defined in that row's file (with its
+    body: a declaration does not count)."""
+    csrc = os.path.join(ROOT, "mazero_amd", "csrc")
+    files = sorted(n for n in os.listdir(csrc) if n.endswith((".hip", ".inc", ".h")))
+    src = {}
+    for n in files:
+        with open(os.path.join(csrc, n)) as f:
+            src[n] = f.read()
+    includes = [m for n in files if n.endswith((".hip", ".inc"))
+                for m in re.findall(r'^[ \t]*#[ \t]*include[ \t]+"([^"]+)"', src[n], flags=re.M)]
+    for n in files:
+        if n.endswith(".inc"):
+            assert includes.count(n) == 1, f"{n} is included {includes.count(n)} times"
+    text = _read("DESIGN.md")
+    sec = text[text.index("### Source map"):text.index("### Build switches")]
+    rows = re.findall(r"^\| `([A-Za-z0-9_.]+)` \|[^|]*\|([^|]*)\|$", sec, flags=re.M)
+    assert sorted(r[0] for r in rows) == files, (sorted(r[0] for r in rows), files)
+    named = 0
+    for name, cell in rows:
+        for k in re.findall(r"`(k_\w+)`", cell):
+            named += 1
+            assert re.search(r"__global__[^;{()]*(\([^()]*\)[^;{()]*)*\bvoid\s+" + k + r"\s*\([^;{]*\{", src[name]), (name, k)
+    assert named, "the Source map names no kernel"
+    # and the other way round: a kernel no row names has no documented home
+    for n in files:
+        cell = dict(rows)[n]
+        for k in re.findall(r"__global__[^;{]*?\bvoid\s+(k_\w+)\s*\(", src[n]):
+            assert f"`{k}`" in cell, (n, k)
