@@ -304,6 +304,13 @@ int mz_arena_info(mz_batch *b, int64_t *out, int n);
  *   path entries are -1 past level 0. */
 int mz_debug_paths(mz_batch *b, int32_t *header, int32_t *path, int max_levels);
 
+/* Diagnostics (tests): every tree's value normaliser as its header carries it into the next launch
+ * -- the minimum and maximum of the tree's q values and their count (CMinMaxStats) -- copied to
+ * host memory after the handle's queued work; mn, mx and cnt hold one element per tree.  In a K = 1
+ * search every node has one child, so no selection depends on the normaliser and a wrong one shows
+ * in no other output. */
+int mz_debug_minmax(mz_batch *b, float *mn, float *mx, int32_t *cnt);
+
 #ifdef __cplusplus
 }
 #endif

@@ -142,6 +142,7 @@ DRIVER_SIGNATURES = {
     "mz_readback_ready": (_i, [_p, _f]),
     "mz_trim_caches": (_i, [C.POINTER(_i64)]),
     "mz_debug_paths": (_i, [_p, _p, _p, _i]),
+    "mz_debug_minmax": (_i, [_p, _p, _p, _p]),
     "mz_arena_info": (_i, [_p, _p, _i]),
 }
 DRIVER_EXPORTS = sorted(DRIVER_SIGNATURES)

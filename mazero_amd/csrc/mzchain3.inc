@@ -83,13 +83,23 @@ typedef const ChainIO cChainIO;
 typedef int int4v __attribute__((ext_vector_type(4)));
 typedef int int8v __attribute__((ext_vector_type(8)));
 typedef int int16v __attribute__((ext_vector_type(16)));
+typedef float float2v __attribute__((ext_vector_type(2)));
 // stores through an address a lane holds in registers (typed as global memory: global_store, not flat)
 #ifdef __HIP_DEVICE_COMPILE__
 typedef __attribute__((address_space(1))) int4v g_int4v;
 typedef __attribute__((address_space(1))) int g_int;
+typedef __attribute__((address_space(1))) float2v g_float2v;
+// and through an LDS address a lane holds as a 32-bit value
+typedef __attribute__((address_space(3))) int4v lds_int4v;
+typedef __attribute__((address_space(3))) float2v lds_float2v;
+typedef __attribute__((address_space(3))) float lds_f32;
 #else
 typedef int4v g_int4v;
 typedef int g_int;
+typedef float2v g_float2v;
+typedef int4v lds_int4v;
+typedef float2v lds_float2v;
+typedef float lds_f32;
 #endif
 __device__ __forceinline__ void st_lane16(uintptr_t p, int4v v) { *(g_int4v *)p = v; }
 __device__ __forceinline__ void st_lane4(uintptr_t p, int v) { *(g_int *)p = v; }
@@ -472,11 +482,41 @@ __global__ __launch_bounds__(W4 ? 256 : 192) void k_chain3(char *base, const flo
         }
         const float g = i2f(g_i);
         // the chain's rewards, reversed: sRv[j] = r_{D-j} (r_D = this simulation's reward)
+        float rw[NCH];  // (the leaf's reward is this simulation's)
 #pragma unroll
         for (int c = 0; c < NCH; ++c) {
             const int i = c * kWave + l;
-            if (i >= 1 && i <= D) sRv[D - i] = (i == D) ? r_in : i2f(a4[c].w);
+            rw[c] = (i == D) ? r_in : i2f(a4[c].w);
+            if (i >= 1 && i <= D) sRv[D - i] = rw[c];
         }
+        // What the node updates need and the recurrence does not feed, here, in the shadow of the
+        // record loads and of the staging round trip, not behind the recurrence on the launch's
+        // chain: the records' store offsets, the LDS offsets of sA / sPP / the lane's key, visit + 1,
+        // the total weight, and i - 1 (one unsigned compare with D is then the lane's "node 1..D").
+        // Pinned with empty asm: the compiler would sink each to its use.
+        // (LDS addresses as 32-bit values: a pinned generic pointer would make the accesses flat.  The
+        // new record is pinned whole, visit + 1, the structure word and the reward in place around the
+        // value's register: no copy in front of the 16-byte stores.)
+        auto lds_of = [&](const void *p) { return (unsigned)(uintptr_t)(lds_void *)p; };
+        unsigned stA[NCH], stC[NCH], pSA[NCH], pSP[NCH], pKey[NCH], im1[NCH];
+        int4v na[NCH];
+        float tw[NCH];
+#pragma unroll
+        for (int c = 0; c < NCH; ++c) {
+            const unsigned i = (unsigned)(c * kWave + l);
+            stA[c] = rA + i * 16, stC[c] = rC + i * 16;  // (kEntry)
+            pSA[c] = lds_of(sA + i), pSP[c] = lds_of(sPP + i);
+            pKey[c] = lds_of(sBv) + ((unsigned)D - 1u - i) * 4;  // sBv[D - 1 - i]
+            im1[c] = i - 1u;
+            na[c] = int4v{a4[c].x + 1, a4[c].y, 0, f2i(rw[c])};
+            tw[c] = cw[c].y + lpv[c];
+            asm volatile("" : "+v"(stA[c]), "+v"(stC[c]), "+v"(pSA[c]), "+v"(pSP[c]), "+v"(pKey[c]), "+v"(im1[c]),
+                         "+v"(na[c]), "+v"(tw[c]));
+        }
+        // the reductions' identities (lanes past the chain keep them) and lane 63's two store addresses
+        float mn = INFINITY, mx = -INFINITY;
+        unsigned pX = lds_of(sX), stH = ((unsigned)t << 8) + (unsigned)(kHdr8 + (int)offsetof(TreeHdr, mm_min));  // (kEntry)
+        asm volatile("" : "+v"(mn), "+v"(mx), "+v"(pX), "+v"(stH));
         wait_lds();
         stamp(ts, 1);
         // b_{D-1-j} = r_{D-j} + discount * b_{D-j}, j = 0 .. D-1, sixteen levels per LDS round
@@ -519,42 +559,42 @@ __global__ __launch_bounds__(W4 ? 256 : 192) void k_chain3(char *base, const flo
         stamp(ts, 2);
         // ---- every node of the chain, lane i = node i: visits, value set (an append to an empty
         // depth class, utils.cpp:36-44), value (cnode.cpp:42-56); min / max over the q of 1..D ----
-        float mn = INFINITY, mx = -INFINITY;
 #pragma unroll
         for (int c = 0; c < NCH; ++c) {
             const int i = c * kWave + l;
             if (i <= D) {
-                const float key = (i == D) ? v_in : sBv[D - 1 - i];
-                const float rw = (i == D) ? r_in : i2f(a4[c].w);  // the leaf's reward is this simulation's
-                const float tw = cw[c].y + lpv[c];
+                // (the read is unconditional -- the leaf's lane reads the word in front of sBv -- so
+                // that the key is one select, not a branch around the read)
+                const float kb = *(const lds_f32 *)(uintptr_t)pKey[c];
+                const float key = (i == D) ? v_in : kb;
                 const float ws = cw[c].x + lpv[c] * key;
-                const float val = ws / tw;
-                const int4 na = make_int4(a4[c].x + 1, a4[c].y, f2i(val), f2i(rw));
+                const float val = ws / tw[c];
+                na[c][2] = f2i(val);
                 if constexpr (kEntry) {
-                    *(int4 *)(d.base + (rA + (unsigned)i * 16)) = na;
-                    *(float2 *)(d.base + (rC + (unsigned)i * 16)) = make_float2(ws, tw);
+                    *(g_int4v *)(d.base + stA[c]) = na[c];
+                    *(g_float2v *)(d.base + stC[c]) = float2v{ws, tw[c]};
                 } else {
-                    d.A()[nb + i] = na;
-                    *(float2 *)&d.C()[nb + i] = make_float2(ws, tw);
+                    d.A()[nb + i] = make_int4(na[c][0], na[c][1], na[c][2], na[c][3]);
+                    *(float2 *)&d.C()[nb + i] = make_float2(ws, tw[c]);
                 }
-                sA[i] = na;
-                sPP[i] = pp[c];
-                if (i >= 1) {
-                    const float q = (rw + g * val) - pp[c];  // get_qsa - father->pred_value
+                *(lds_int4v *)(uintptr_t)pSA[c] = na[c];  // sA[i]
+                *(lds_f32 *)(uintptr_t)pSP[c] = pp[c];    // sPP[i]
+                if (im1[c] < (unsigned)D) {               // node 1..D
+                    const float q = (rw[c] + g * val) - pp[c];  // get_qsa - father->pred_value
                     mn = fminf(mn, q);
                     mx = fmaxf(mx, q);
                 }
             }
         }
-        mn = unif(rlf(wave_min_to63(mn), 63));
-        mx = unif(rlf(wave_max_to63(mx), 63));
-        if (l == 0) {
-            sX[0] = mn;
-            sX[1] = mx;
+        // both reductions at once; lane 63 holds the two results and stores them itself, the pair
+        // in one 8-byte store each to LDS and to the header (no v_readlane, no lane 0)
+        wave_minmax_to63(mn, mx);
+        if (l == kWave - 1) {
+            *(lds_float2v *)(uintptr_t)pX = float2v{mn, mx};  // sX[0], sX[1]
             // (the header's normaliser is this wave's: wave 0 skips the barrier in select_walk's
             // fast case and writes the rest of the header)
-            hp->mm_min = mn;
-            hp->mm_max = mx;
+            if constexpr (kEntry) *(g_float2v *)(d.base + stH) = float2v{mn, mx};  // mm_min, mm_max
+            else *(float2 *)&hp->mm_min = make_float2(mn, mx);
             if (MZ_STAMPS) {
                 sXl[0] = (long long)(ts[2] - ts[1]);                         // the recurrence
                 sXl[1] = (long long)(__builtin_amdgcn_s_memtime() - ts[2]);  // node updates

@@ -579,6 +579,49 @@ __device__ __forceinline__ float wave_max_to63(float v) {
     v = fmaxf(v, i2f(__builtin_amdgcn_update_dpp(f2i(v), f2i(v), 0x143, 0xc, 0xf, false)));
     return v;
 }
+// Both at once, for a wave that ends on them: the same six steps with the DPP control on the
+// v_min_f32 / v_max_f32 itself (no copy, no v_mov_b32_dpp) and the two chains interleaved, in one
+// statement the compiler cannot pull apart.  Exact in lane 63 only, as the two above.
+// Bit-identical to them unless an operand is a signalling NaN: fminf / fmaxf compile to a
+// canonicalising v_max_f32 x, x, x in front of each v_min_f32 / v_max_f32, which only ever changes a
+// signalling NaN, and in IEEE mode (the kernel descriptor's default, unchanged) the bare instruction
+// returns the other operand for a quiet NaN, as fminf / fmaxf do.  The operands here are results of
+// f32 arithmetic or the +-INFINITY initialisers: never signalling.
+// Wait states (the compiler pads nothing inside an asm statement, and does not see that its
+// instructions are DPP; CDNA3/4 ISA guide, "Manually Inserted Wait States"):
+//  - a VALU write of a VGPR needs 2 states before a DPP read of it; a VALU write of EXEC needs 5
+//    before any DPP instruction.  The operands and the exec mask in front of the statement are the
+//    compiler's, so the string opens with s_nop 4 (5 states: covers both);
+//  - inside, each chain's step reads what its previous step wrote: the other chain's instruction is
+//    one state, s_nop 0 the second;
+//  - the string ends with s_nop 1, so that a DPP read of either result by the compiler's next
+//    instruction has its 2 states too (a plain VALU read or a store's data read needs none).
+// Rows a step's row_mask leaves out, and lanes whose DPP source is invalid (row 0 under row_bcast:15),
+// are not written (bound_ctrl off): the old helpers' min(v, v).  All lanes must be active, in
+// wave-uniform control flow.
+__device__ __forceinline__ void wave_minmax_to63(float &mn, float &mx) {
+    asm volatile(
+        "s_nop 4\n\t"
+        "v_min_f32_dpp %0, %0, %0 quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf\n\t"
+        "v_max_f32_dpp %1, %1, %1 quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf\n\t"
+        "s_nop 0\n\t"
+        "v_min_f32_dpp %0, %0, %0 quad_perm:[2,3,0,1] row_mask:0xf bank_mask:0xf\n\t"
+        "v_max_f32_dpp %1, %1, %1 quad_perm:[2,3,0,1] row_mask:0xf bank_mask:0xf\n\t"
+        "s_nop 0\n\t"
+        "v_min_f32_dpp %0, %0, %0 row_half_mirror row_mask:0xf bank_mask:0xf\n\t"
+        "v_max_f32_dpp %1, %1, %1 row_half_mirror row_mask:0xf bank_mask:0xf\n\t"
+        "s_nop 0\n\t"
+        "v_min_f32_dpp %0, %0, %0 row_mirror row_mask:0xf bank_mask:0xf\n\t"
+        "v_max_f32_dpp %1, %1, %1 row_mirror row_mask:0xf bank_mask:0xf\n\t"
+        "s_nop 0\n\t"
+        "v_min_f32_dpp %0, %0, %0 row_bcast:15 row_mask:0xa bank_mask:0xf\n\t"
+        "v_max_f32_dpp %1, %1, %1 row_bcast:15 row_mask:0xa bank_mask:0xf\n\t"
+        "s_nop 0\n\t"
+        "v_min_f32_dpp %0, %0, %0 row_bcast:31 row_mask:0xc bank_mask:0xf\n\t"
+        "v_max_f32_dpp %1, %1, %1 row_bcast:31 row_mask:0xc bank_mask:0xf\n\t"
+        "s_nop 1"
+        : "+v"(mn), "+v"(mx));
+}
 __device__ __forceinline__ int wave_sum(int v) {
     v += dpp<0xB1>(v);
     v += dpp<0x4E>(v);
@@ -1933,8 +1976,7 @@ __device__ __forceinline__ void backup(const Geo &g, const Dev &d, Lds &s, int t
         }
         cv += __popcll(ballot(on));
     }
-    mn = wave_min_to63(mn);
-    mx = wave_max_to63(mx);
+    wave_minmax_to63(mn, mx);
     if (l == 63) {
         xmm[0] = mn;
         xmm[1] = mx;
@@ -3191,8 +3233,9 @@ __global__ __launch_bounds__(128) void k_chain(char *base, const float *policy, 
             }
         }
         // min / max over the q of the visited non-root nodes: the whole chain 1..D
-        mn = unif(rlf(wave_min_to63(mn), 63));
-        mx = unif(rlf(wave_max_to63(mx), 63));
+        wave_minmax_to63(mn, mx);
+        mn = unif(rlf(mn, 63));
+        mx = unif(rlf(mx, 63));
         if (l == 0) {
             sR[2] = mn;
             sR[3] = mx;
@@ -4325,8 +4368,9 @@ __global__ __launch_bounds__(kTreeWavesN<NC> * 64) void k_tree(char *base, const
             }
         }
         cv = wave_sum(cv);
-        mn = fminf(wave_min_to63(mn), bmn);  // (with this wave's path nodes)
-        mx = fmaxf(wave_max_to63(mx), bmx);
+        wave_minmax_to63(mn, mx);
+        mn = fminf(mn, bmn);  // (with this wave's path nodes)
+        mx = fmaxf(mx, bmx);
         if (l == 63) {
             xbo[wv].mn = mn;
             xbo[wv].mx = mx;
@@ -7654,6 +7698,23 @@ int mz_debug_paths(mz_batch *b, int32_t *header, int32_t *path, int max_levels) 
                 po[3] = i == 0 ? -1 : (r.y >> 8) & 0xff;
             }
         }
+    }
+    return MZ_OK;
+}
+
+int mz_debug_minmax(mz_batch *b, float *mn, float *mx, int32_t *cnt) {
+    if (!b || !mn || !mx || !cnt) return fail(MZ_ERR_ARG, "mz_debug_minmax: bad argument");
+    int rc = ensure_device(b);
+    if (rc) return rc;
+    rc = flush_pending(b);
+    if (rc) return rc;
+    std::vector<TreeHdr> h(b->B);
+    HIP_TRY(hipMemcpyAsync(h.data(), b->dev.hdr(), sizeof(TreeHdr) * h.size(), hipMemcpyDeviceToHost, b->stream));
+    HIP_TRY(hipStreamSynchronize(b->stream));
+    for (int t = 0; t < b->B; ++t) {
+        mn[t] = h[t].mm_min;
+        mx[t] = h[t].mm_max;
+        cnt[t] = h[t].mm_cnt;
     }
     return MZ_OK;
 }

@@ -528,6 +528,17 @@ class Tree_batch:
         check(self._lib, self._lib.mz_prepare_kernel(self._h, buf, len(buf)), "prepare_kernel")
         return buf.value.decode()
 
+    def debug_minmax(self):
+        """Every tree's value normaliser as its header holds it after the queued work: (min [B],
+        max [B], count [B]); include/mzdriver.h mz_debug_minmax (product library only)."""
+        B = self.root_num
+        mn, mx, cnt = np.empty(B, np.float32), np.empty(B, np.float32), np.empty(B, np.int32)
+        self._sync_stream()
+        check(self._lib, self._lib.mz_debug_minmax(self._h, mn.ctypes.data_as(C.c_void_p),
+                                                   mx.ctypes.data_as(C.c_void_p), cnt.ctypes.data_as(C.c_void_p)),
+              "debug_minmax")
+        return mn, mx, cnt
+
     def synchronize(self):
         self._sync_stream()
         check(self._lib, self._lib.mz_synchronize(self._h), "synchronize")
