@@ -17,6 +17,11 @@ Reported, as one JSON line:
   agents' greedy actions of every simulation come from a per-node cache (mz_policy_glue_later,
   mz_joint_action_cached) instead of a prediction pass on the selected leaves. Its own
   `actions_equal_device`, and the recorded graphs' node counts per agent without and with the cache.
+- `device_joint`: `SampledMCTS.batch_search_joint`, ONE search over joint-action trees per
+  environment step (the call of the reference's evaluation loop, core/test.py:84) at the same shape,
+  with its recorded graph's node count and the tree kernel; `other_sampled_times` is the same at K = 5
+  beside K = 1. Another algorithm with other search results than the N per-agent searches: its
+  `ms_per_step` beside `device`'s is a cost per environment step, not an A/B.
 - `device_eager`: the same driver without graphs.
 - `selfplay_step_host_consumers` / `selfplay_step_device_consumers`: a whole self-play step with
   its per-root decisions (select_action, epsilon-greedy, recorded policy probability,
@@ -136,6 +141,33 @@ def main():
                                   "actions_equal_device": bool(same_actions),
                                   "graph_nodes_per_agent": {"fused_transforms": nodes[False],
                                                             "later_cache": nodes[True]}}
+    # The joint search (SampledMCTS.batch_search_joint): ONE search over joint-action trees per
+    # environment step instead of N per-agent searches.  Another algorithm with other search results
+    # (K sampled joint actions per node, no estimate of the other agents' actions), so the figure beside
+    # `device` is a cost per environment step, not an A/B.  At the legs' K, and at K = 5 beside K = 1.
+    def joint_leg(k):
+        jcfg = SearchConfig(action_space_size=A, num_simulations=S, sampled_action_times=k)
+        mcts = SampledMCTS(jcfg, np.random.RandomState(0), use_graph=True)
+
+        def joint_step(i):
+            out, legal = roots[i % len(roots)]
+            return mcts.batch_search_joint(net, out, legal, dev, True, 1.0)
+
+        for i in range(2):
+            joint_step(i)
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for i in range(args.steps):
+            joint_step(i)
+        torch.cuda.synchronize()
+        tj = (time.perf_counter() - t0) / args.steps
+        loop = [v for v in _LOOPS.values() if v.joint_mode and v.model_ref() is net and v.tb.agent_num == N
+                and v.graph_nodes][-1]
+        return {"sampled_times": k, "value": round(B * S / tj, 1), "ms_per_step": round(tj * 1e3, 3),
+                "searches_per_step": 1, "graph_nodes": loop.graph_nodes[0], "fused_kernel": loop.tb.fused_kernel()}
+
+    line["device_joint"] = joint_leg(K)
+    line["device_joint"]["other_sampled_times"] = joint_leg(5 if K == 1 else 1)
     if args.device_only:
         line["steps"] = args.steps
         print(json.dumps(line), flush=True)

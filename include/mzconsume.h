@@ -56,6 +56,16 @@ int mz_select_actions(mz_batch *b, const int32_t *degrees, const int32_t *visits
                       int width, double temperature, int deterministic, const double *uniforms, int32_t *pos_out,
                       int32_t *action_out, double *entropy_out);
 
+/* mz_select_actions for a joint search (a handle of agent_num = N > 1, one search for all agents): the
+ * same arguments, checks and arithmetic, and action_out is int32 [B, N], the chosen child's whole joint
+ * action actions[i, pos * N .. pos * N + N) -- `roots_sampled_actions[i][action_pos]` of the reference's
+ * evaluation loop (core/test.py:101-107, which calls select_action with deterministic=True).  A root
+ * without children or visits gets -1 in pos_out and in every column of its action row.  With N = 1 the
+ * results are those of mz_select_actions. */
+int mz_select_actions_joint(mz_batch *b, const int32_t *degrees, const int32_t *visits, const int32_t *actions,
+                            int width, double temperature, int deterministic, const double *uniforms,
+                            int32_t *pos_out, int32_t *action_out, double *entropy_out);
+
 /* eps_greedy_action(greedy, legal_mask, eps) (core/utils.py:319-334) for every root:
  *   action_io = (u_eps[i] < (float)eps) ? categorical(legal[i, :]; u_cat[i]) : action_io[i]
  * legal: int32 [B, A] (row stride legal_stride elements), the agent's legal-action weights;

@@ -100,7 +100,10 @@ int mz_readback_ready(mz_batch *b, float discount);
 /* Policy glue of one simulation (mcts_sampled.py:156-161 and 169-170).
  * logits: the network's policy logits [B, num_agents, A] (row stride `row_stride` elements,
  * the current agent's A logits start at element `col_offset` of a row), dtype `dtype`.
- * probs_out, beta_out: float32 [B, A] (= [B, 1, A]).  sampled_tau: the Python float. */
+ * probs_out, beta_out: float32 [B, A] (= [B, 1, A]).  sampled_tau: the Python float.
+ * A row whose exponentials sum to a NaN (it holds a NaN, or its maximum is infinite: inf - inf) is a NaN
+ * in every element of both outputs, the NaN numpy on x86-64 writes there: the positive quiet NaN, or
+ * the negative one for a float16 row that holds no NaN of its own. */
 int mz_policy_glue(mz_batch *b, const void *logits, int dtype, int64_t row_stride, int64_t col_offset,
                    double sampled_tau, float *probs_out, float *beta_out);
 
@@ -197,6 +200,26 @@ int mz_policy_glue_later(mz_batch *b, const void *logits, int dtype, int64_t row
 int mz_joint_action_cached(mz_batch *b, const int32_t *later_pool, int slots, const int32_t *idx_x,
                            int num_agents, int current_agent, const int32_t *factor, int factor_cols,
                            const int32_t *actions, int64_t *joint_out);
+
+/* The glue of a joint search (a handle of agent_num = N > 1, whose prepare and expansion take
+ * [B, N, A] policy, beta and noise): every agent's row in one launch, one wave per (root, agent).
+ * The row code is that of mz_policy_glue / mz_root_glue, so for every agent k the slice [:, k, :] of an
+ * output holds the bytes of the narrow call with col_offset = k * A on the agent's own columns.
+ * Nothing is allocated or uploaded, so the calls can be captured in a graph.  action_space_size > 64 is
+ * MZ_ERR_UNSUPPORTED (one lane per action; joint trees take no more); num_agents need not be the
+ * handle's agent_num (the handle gives B, A and the stream).
+ *
+ * mz_policy_glue_joint: logits [B, num_agents, A] of dtype `dtype`, row stride `row_stride` >=
+ * num_agents * A elements; probs_out, beta_out float32 [B, num_agents, A].
+ *
+ * mz_root_glue_joint: logits as above; legal int32 [B, legal_stride] rows whose element k * A + a is
+ * agent k's mask of action a (legal_stride >= num_agents * A), or NULL; noises float32
+ * [B, num_agents, A]; probs_out, beta_out, noises_out float32 [B, num_agents, A]. */
+int mz_policy_glue_joint(mz_batch *b, const void *logits, int dtype, int64_t row_stride, int num_agents,
+                         double sampled_tau, float *probs_out, float *beta_out);
+int mz_root_glue_joint(mz_batch *b, const void *logits, int dtype, int64_t row_stride, int num_agents,
+                       const int32_t *legal, int64_t legal_stride, const float *noises, double noise_eps,
+                       double sampled_tau, float *probs_out, float *beta_out, float *noises_out);
 
 /* Inverse support transform of the value and the reward head of one simulation: what
  * MAMuZeroNet.recurrent_inference applies to the two heads' logits in eval mode

@@ -128,6 +128,11 @@ DRIVER_SIGNATURES = {
     # num_agents, current_agent, factor, factor_cols, actions, joint_out)
     "mz_policy_glue_later": (_i, [_p, _p, _i, _i64, _i, _i, C.c_double, _p, _p, _p]),
     "mz_joint_action_cached": (_i, [_p, _p, _i, _p, _i, _i, _p, _i, _p, _p]),
+    # the glue of a joint search, every agent in one launch: (handle, logits, dtype, row_stride, num_agents,
+    # sampled_tau, probs_out, beta_out) and (handle, logits, dtype, row_stride, num_agents, legal,
+    # legal_stride, noises, noise_eps, sampled_tau, probs_out, beta_out, noises_out)
+    "mz_policy_glue_joint": (_i, [_p, _p, _i, _i64, _i, C.c_double, _p, _p]),
+    "mz_root_glue_joint": (_i, [_p, _p, _i, _i64, _i, _p, _i64, _p, C.c_double, C.c_double, _p, _p, _p]),
     # (handle or NULL, stream, stage, n, value head: in, dtype, stride, lo, hi; reward head likewise; outputs)
     "mz_inverse_transform": (_i, [_p, _p, _i, _i, _p, _i, _i64, _i, _i, _p, _i, _i64, _i, _i, _p, _p]),
     "mz_inverse_transform_wide": (_i, [_p, _p, _i, _i, _p, _i, _i64, _i, _i, _p, _i, _i64, _i, _i, _p, _p]),
@@ -151,6 +156,7 @@ DRIVER_EXPORTS = sorted(DRIVER_SIGNATURES)
 MZ_MARGINAL_GIVEN, MZ_MARGINAL_ARGMAX, MZ_MARGINAL_ARGMAX_LEGAL = 0, 1, 2  # enum mz_marginal_mode
 CONSUME_SIGNATURES = {
     "mz_select_actions": (_i, [_p, _p, _p, _p, _i, C.c_double, _i, _p, _p, _p, _p]),
+    "mz_select_actions_joint": (_i, [_p, _p, _p, _p, _i, C.c_double, _i, _p, _p, _p, _p]),  # action_out [B, N]
     "mz_eps_greedy": (_i, [_p, _p, _i64, _f, _p, _p, _p]),
     "mz_marginal_policy": (_i, [_p, _p, _i64, _p, _i64, _i, _p, _p, _p]),
     # reanalyze batch targets: (handle or NULL, stream, ...)

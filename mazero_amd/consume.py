@@ -97,6 +97,38 @@ def select_actions(out: DeviceSearchOutput, uniforms: Optional[torch.Tensor], te
     return pos, act, ent
 
 
+def select_joint_actions(out: DeviceSearchOutput, temperature: float = 1.0, deterministic: bool = True,
+                         uniforms: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """select_action at every root of a joint search (SampledMCTS.batch_search_joint_device) and the
+    chosen child's whole joint action, `roots_sampled_actions[i][action_pos]` -> (actions int32 [B, N],
+    pos int32 [B], count entropy float64 [B]) device tensors.  With the default `deterministic=True`
+    this is the reference's evaluation step (core/test.py:101-107); otherwise `uniforms` holds the
+    doubles `np_random.choice` would draw, float64 [B] in root order.  A root without children or visits
+    gets -1 in `pos` and in every column of its action row."""
+    tb = _tree(out)
+    visits = out.sampled["visit_count"].contiguous()
+    actions = out.sampled["actions"].contiguous()
+    B, width = visits.shape
+    N = tb.agent_num
+    if actions.shape != (B, width * N):
+        raise ValueError(f"sampled actions of shape {tuple(actions.shape)} for {B} roots, {width} children and "
+                         f"{N} agents")
+    dev = visits.device
+    if not deterministic:
+        uniforms = torch.as_tensor(uniforms, dtype=torch.float64).to(dev).contiguous()
+        if uniforms.shape != (B,):
+            raise ValueError(f"uniforms must have shape ({B},)")
+    pos = torch.empty(B, dtype=torch.int32, device=dev)
+    act = torch.empty(B, N, dtype=torch.int32, device=dev)
+    ent = torch.empty(B, dtype=torch.float64, device=dev)
+    lib = tb._lib
+    check(lib, lib.mz_select_actions_joint(tb._h, _p(out.degrees), _p(visits), _p(actions), int(width),
+                                           float(temperature), int(bool(deterministic)),
+                                           None if deterministic else _p(uniforms), _p(pos), _p(act), _p(ent)),
+          "select_joint_actions")
+    return act, pos, ent
+
+
 def eps_greedy(out: DeviceSearchOutput, action: torch.Tensor, legal: torch.Tensor, eps: float,
                u_eps: torch.Tensor, u_cat: torch.Tensor) -> torch.Tensor:
     """eps_greedy_action (core/utils.py:319-334) at every root, in place on `action` (int32 [B]).

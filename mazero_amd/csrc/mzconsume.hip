@@ -17,6 +17,7 @@
 
 #include <algorithm>
 #include <mutex>
+#include <string>
 #include <vector>
 
 #include "../../include/mzconsume.h"
@@ -37,23 +38,21 @@ __device__ __forceinline__ double visit_pow(int v, int ipow, double e) {
     return r;
 }
 
-__global__ __launch_bounds__(kLanes) void k_select_actions(int B, int N, const int *__restrict__ deg,
-                                                           const int *__restrict__ visits,
-                                                           const int *__restrict__ actions, int width, int ipow,
-                                                           double e, int deterministic,
-                                                           const double *__restrict__ uniforms, int *pos_out,
-                                                           int *act_out, double *ent_out) {
-    const int i = blockIdx.x * kLanes + threadIdx.x;
-    if (i >= B) return;
+// select_action for root i (core/utils.py:289-316): the chosen child's position, written to pos_out
+// with the entropy; -1 for a root without children or visits.  The body of k_select_actions and of
+// k_select_actions_joint, which differ in the action columns they copy.
+__device__ __forceinline__ int select_position(int i, const int *__restrict__ deg, const int *__restrict__ visits,
+                                               int width, int ipow, double e, int deterministic,
+                                               const double *__restrict__ uniforms, int *pos_out, double *ent_out) {
     const int n = deg[i];
     const int *row = visits + (long long)i * width;
     long long vsum = 0;
-    for (int j = 0; j < n; ++j) vsum += row[j];
+    if (n <= width)  // (a degree past the row's width is refused below, and never read)
+        for (int j = 0; j < n; ++j) vsum += row[j];
     if (n <= 0 || n > width || vsum <= 0) {  // assert sum(visit_counts) > 0 (core/utils.py:301)
         pos_out[i] = -1;
-        act_out[i] = -1;
         if (ent_out) ent_out[i] = NAN;
-        return;
+        return -1;
     }
     // total_count = sum(action_probs): Python's sum, left to right from 0 (utils.py:304)
     double total = 0.0;
@@ -79,7 +78,6 @@ __global__ __launch_bounds__(kLanes) void k_select_actions(int B, int N, const i
         }
     }
     pos_out[i] = pos;
-    act_out[i] = actions[(long long)i * width * N + (long long)pos * N];  // sampled_actions[pos, 0]
     if (ent_out) {
         // scipy.stats.entropy(action_probs, base=2): pk / sum(pk), sum of -pk log pk, / log(2)
         double ps = 0.0;
@@ -91,6 +89,35 @@ __global__ __launch_bounds__(kLanes) void k_select_actions(int B, int N, const i
         }
         ent_out[i] = h / log(2.0);
     }
+    return pos;
+}
+
+__global__ __launch_bounds__(kLanes) void k_select_actions(int B, int N, const int *__restrict__ deg,
+                                                           const int *__restrict__ visits,
+                                                           const int *__restrict__ actions, int width, int ipow,
+                                                           double e, int deterministic,
+                                                           const double *__restrict__ uniforms, int *pos_out,
+                                                           int *act_out, double *ent_out) {
+    const int i = blockIdx.x * kLanes + threadIdx.x;
+    if (i >= B) return;
+    const int pos = select_position(i, deg, visits, width, ipow, e, deterministic, uniforms, pos_out, ent_out);
+    // sampled_actions[pos, 0]
+    act_out[i] = pos < 0 ? -1 : actions[(long long)i * width * N + (long long)pos * N];
+}
+
+// mz_select_actions_joint: the chosen child's whole joint action, sampled_actions[pos] (core/test.py:
+// 101-107), into row i of act_out [B, N]
+__global__ __launch_bounds__(kLanes) void k_select_actions_joint(int B, int N, const int *__restrict__ deg,
+                                                                 const int *__restrict__ visits,
+                                                                 const int *__restrict__ actions, int width,
+                                                                 int ipow, double e, int deterministic,
+                                                                 const double *__restrict__ uniforms, int *pos_out,
+                                                                 int *act_out, double *ent_out) {
+    const int i = blockIdx.x * kLanes + threadIdx.x;
+    if (i >= B) return;
+    const int pos = select_position(i, deg, visits, width, ipow, e, deterministic, uniforms, pos_out, ent_out);
+    for (int k = 0; k < N; ++k)
+        act_out[(long long)i * N + k] = pos < 0 ? -1 : actions[((long long)i * width + pos) * N + k];
 }
 
 __global__ __launch_bounds__(kLanes) void k_eps_greedy(int B, int A, const int *__restrict__ legal, long long stride,
@@ -450,24 +477,41 @@ int launch_status() {
 
 extern "C" {
 
-int mz_select_actions(mz_batch *b, const int32_t *degrees, const int32_t *visits, const int32_t *actions, int width,
-                      double temperature, int deterministic, const double *uniforms, int32_t *pos_out,
-                      int32_t *action_out, double *entropy_out) {
+// mz_select_actions (joint false: agent 0's action, [B]) and mz_select_actions_joint ([B, N])
+static int select_actions(const char *fn, bool joint, mz_batch *b, const int32_t *degrees, const int32_t *visits,
+                          const int32_t *actions, int width, double temperature, int deterministic,
+                          const double *uniforms, int32_t *pos_out, int32_t *action_out, double *entropy_out) {
     int B = 0, A = 0;
     hipStream_t stream = nullptr;
     int rc = consumer_info(b, &B, &A, &stream);
     if (rc) return rc;
+    const std::string name(fn);
     if (!degrees || !visits || !actions || !pos_out || !action_out || (!deterministic && !uniforms))
-        return mz_internal_fail(MZ_ERR_ARG, "mz_select_actions: null buffer");
-    if (width < 1) return mz_internal_fail(MZ_ERR_ARG, "mz_select_actions: width must be >= 1");
-    if (!(temperature > 0.0)) return mz_internal_fail(MZ_ERR_ARG, "mz_select_actions: temperature must be > 0");
+        return mz_internal_fail(MZ_ERR_ARG, (name + ": null buffer").c_str());
+    if (width < 1) return mz_internal_fail(MZ_ERR_ARG, (name + ": width must be >= 1").c_str());
+    if (!(temperature > 0.0)) return mz_internal_fail(MZ_ERR_ARG, (name + ": temperature must be > 0").c_str());
     const double e = 1.0 / temperature;  // 1 / temperature, as Python computes it
     const int ipow = (e == floor(e) && e >= 1.0 && e <= 8.0) ? (int)e : 0;
-    hipLaunchKernelGGL(k_select_actions, dim3((B + kLanes - 1) / kLanes), dim3(kLanes), 0, stream, B,
-                       mz_internal_agent_num(b), (const int *)degrees, (const int *)visits, (const int *)actions,
-                       width, ipow, e, deterministic, uniforms, (int *)pos_out, (int *)action_out, entropy_out);
+    hipLaunchKernelGGL(joint ? k_select_actions_joint : k_select_actions, dim3((B + kLanes - 1) / kLanes),
+                       dim3(kLanes), 0, stream, B, mz_internal_agent_num(b), (const int *)degrees,
+                       (const int *)visits, (const int *)actions, width, ipow, e, deterministic, uniforms,
+                       (int *)pos_out, (int *)action_out, entropy_out);
     mz_internal_enqueued(b);
     return launch_status();
+}
+
+int mz_select_actions(mz_batch *b, const int32_t *degrees, const int32_t *visits, const int32_t *actions, int width,
+                      double temperature, int deterministic, const double *uniforms, int32_t *pos_out,
+                      int32_t *action_out, double *entropy_out) {
+    return select_actions("mz_select_actions", false, b, degrees, visits, actions, width, temperature, deterministic,
+                          uniforms, pos_out, action_out, entropy_out);
+}
+
+int mz_select_actions_joint(mz_batch *b, const int32_t *degrees, const int32_t *visits, const int32_t *actions,
+                            int width, double temperature, int deterministic, const double *uniforms,
+                            int32_t *pos_out, int32_t *action_out, double *entropy_out) {
+    return select_actions("mz_select_actions_joint", true, b, degrees, visits, actions, width, temperature,
+                          deterministic, uniforms, pos_out, action_out, entropy_out);
 }
 
 int mz_eps_greedy(mz_batch *b, const int32_t *legal, int64_t legal_stride, float eps, const float *u_eps,

@@ -145,12 +145,26 @@ int pow_mode(double inv) {
     return inv == 1.0 ? 0 : inv == 2.0 ? kPowSquare : inv == 0.5 ? kPowSqrt : kPowGeneral;
 }
 
+// The softmax of a row whose exponentials sum to a NaN -- the row holds a NaN, or its maximum is
+// infinite, so that x - max is inf - inf -- is a NaN in every element, and so is beta.  Which NaN is the
+// host's arithmetic, not the GPU's (whose subtraction negates a NaN second operand, sign included):
+// x86-64 hands a NaN operand on as it stands (np.nan: the positive quiet NaN) and answers inf - inf with
+// its default NaN, the negative one; numpy's float32 exp returns the positive quiet NaN for either,
+// its float16 loops keep the sign.  So the element is set by hand: negative only for a float16 row
+// without a NaN of its own.
+template <bool F16>
+__device__ __forceinline__ float np_softmax_nan(bool nan_any) {
+    return __uint_as_float((F16 && !nan_any) ? 0xffc00000u : 0x7fc00000u);
+}
+
 // mcts_sampled.py:158-161 (+ .astype(np.float32), :169-170) for root t, lane l of its wave: the body
-// of k_policy_glue and of role 0 of k_policy_glue_later (lds[kWave] and acc[9] are the workgroup's).
+// of k_policy_glue, of role 0 of k_policy_glue_later and of k_policy_glue_joint (lds[kWave] and acc[9]
+// are the workgroup's).  The A results go to row `out_row` of probs / beta.
 template <bool F16>
 __device__ __forceinline__ void policy_glue_row(const void *logits, long long row_stride, long long col_off, int A,
                                                 int use_pow, float tau_inv, float *probs, float *beta,
-                                                const unsigned short *hexp, int t, int l, float *lds, float *acc) {
+                                                const unsigned short *hexp, int t, long long out_row, int l,
+                                                float *lds, float *acc) {
     const bool on = l < A;
     const float x = on ? load_elem<F16>(logits, (long long)t * row_stride + col_off + l) : -INFINITY;
     // np.max(..., axis=-1): NaN propagates
@@ -164,9 +178,10 @@ __device__ __forceinline__ void policy_glue_row(const void *logits, long long ro
     const float q = use_pow ? np_pow_as<F16>(p, tau_inv, use_pow) : p;
     const float s2 = round_as<F16>(np_row_sum(q, l, A, lds, acc));
     const float b = round_as<F16>(q / s2);
+    const bool nan_row = s != s;  // (the sum is every lane's: the whole row)
     if (on) {
-        probs[(long long)t * A + l] = p;
-        beta[(long long)t * A + l] = b;
+        probs[out_row * A + l] = nan_row ? np_softmax_nan<F16>(nan_any) : p;
+        beta[out_row * A + l] = nan_row ? np_softmax_nan<F16>(nan_any) : b;
     }
 }
 
@@ -177,7 +192,21 @@ __global__ __launch_bounds__(kWave) void k_policy_glue(const void *logits, long 
     __shared__ float lds[kWave];
     __shared__ float acc[9];
     policy_glue_row<F16>(logits, row_stride, col_off, A, use_pow, tau_inv, probs, beta, hexp, blockIdx.x,
-                         threadIdx.x, lds, acc);
+                         blockIdx.x, threadIdx.x, lds, acc);
+}
+
+// mz_policy_glue_joint: k_policy_glue for every agent of a joint search in one launch, one wave per
+// (root, agent), workgroup t * N + k.  Agent k's logits start at element k * A of root t's row and its
+// results are row t * N + k of the [B, N, A] outputs: the row code is k_policy_glue's own.
+template <bool F16>
+__global__ __launch_bounds__(kWave) void k_policy_glue_joint(const void *logits, long long row_stride, int N, int A,
+                                                             int use_pow, float tau_inv, float *probs, float *beta,
+                                                             const unsigned short *hexp) {
+    __shared__ float lds[kWave];
+    __shared__ float acc[9];
+    const int t = (int)(blockIdx.x / (unsigned)N), k = (int)(blockIdx.x % (unsigned)N);
+    policy_glue_row<F16>(logits, row_stride, (long long)k * A, A, use_pow, tau_inv, probs, beta, hexp, t,
+                         (long long)blockIdx.x, threadIdx.x, lds, acc);
 }
 
 // np.argmax of the row of A <= 64 elements that starts at element `row` (mcts_sampled.py:136-145): the
@@ -244,16 +273,17 @@ __device__ __forceinline__ float store_d(double v) {
 //   beta **= 1 / tau; beta *= legal (float64, stored float32); beta /= sum(beta)          :94-100
 // `legal` holds the agent's row as int32 (the caller checked the integer array's values fit), or is
 // null.  The Dirichlet noise is drawn by the caller (np_random order) and arrives as float32.
+// The body of k_root_glue and of k_root_glue_joint for root t, lane l of its wave: the agent's logits
+// start at element col_off of the root's row, its legal mask at element legal_off of the root's legal
+// row; the noise is read from, and the A results go to, row `out_row` of [rows, A] arrays (lds[kWave]
+// and acc[9] are the workgroup's).
 template <bool F16>
-__global__ __launch_bounds__(kWave) void k_root_glue(const void *logits, long long row_stride, long long col_off,
-                                                     int A, const int *legal, long long legal_stride,
-                                                     const float *noise_in, double one_minus_eps, double eps,
-                                                     int use_pow, float tau_inv, float *probs, float *beta,
-                                                     float *noise_out, const unsigned short *hexp) {
-    __shared__ float lds[kWave];
-    __shared__ float acc[9];
-    const int t = blockIdx.x;
-    const int l = threadIdx.x;
+__device__ __forceinline__ void root_glue_row(const void *logits, long long row_stride, long long col_off, int A,
+                                              const int *legal, long long legal_stride, long long legal_off,
+                                              const float *noise_in, double one_minus_eps, double eps, int use_pow,
+                                              float tau_inv, float *probs, float *beta, float *noise_out,
+                                              const unsigned short *hexp, int t, long long out_row, int l,
+                                              float *lds, float *acc) {
     const bool on = l < A;
     const float x = on ? load_elem<F16>(logits, (long long)t * row_stride + col_off + l) : -INFINITY;
     const bool nan_any = __ballot(on && (x != x)) != 0;
@@ -262,10 +292,10 @@ __global__ __launch_bounds__(kWave) void k_root_glue(const void *logits, long lo
     const float e = np_exp_as<F16>(d, hexp);
     const float s = round_as<F16>(np_row_sum(e, l, A, lds, acc));
     float p = round_as<F16>(e / s);
-    float n = on ? noise_in[(long long)t * A + l] : 0.f;
+    float n = on ? noise_in[out_row * A + l] : 0.f;
     double lg = 0.0;
     if (legal) {
-        lg = on ? (double)legal[(long long)t * legal_stride + l] : 0.0;
+        lg = on ? (double)legal[(long long)t * legal_stride + legal_off + l] : 0.0;
         const double tiny = lg * 1e-4;  // `legal * 1e-4`: a float64 array
         p = store_d<F16>((double)p * lg);
         p = store_d<F16>((double)p + tiny);
@@ -286,10 +316,39 @@ __global__ __launch_bounds__(kWave) void k_root_glue(const void *logits, long lo
     const float sb = np_row_sum(b, l, A, lds, acc);
     b = b / sb;
     if (on) {
-        probs[(long long)t * A + l] = p;
-        beta[(long long)t * A + l] = b;
-        noise_out[(long long)t * A + l] = n;
+        probs[out_row * A + l] = p;
+        beta[out_row * A + l] = b;
+        noise_out[out_row * A + l] = n;
     }
+}
+
+template <bool F16>
+__global__ __launch_bounds__(kWave) void k_root_glue(const void *logits, long long row_stride, long long col_off,
+                                                     int A, const int *legal, long long legal_stride,
+                                                     const float *noise_in, double one_minus_eps, double eps,
+                                                     int use_pow, float tau_inv, float *probs, float *beta,
+                                                     float *noise_out, const unsigned short *hexp) {
+    __shared__ float lds[kWave];
+    __shared__ float acc[9];
+    root_glue_row<F16>(logits, row_stride, col_off, A, legal, legal_stride, 0, noise_in, one_minus_eps, eps, use_pow,
+                       tau_inv, probs, beta, noise_out, hexp, blockIdx.x, blockIdx.x, threadIdx.x, lds, acc);
+}
+
+// mz_root_glue_joint: k_root_glue for every agent of a joint search in one launch, one wave per
+// (root, agent), workgroup t * N + k.  Agent k's logits and legal mask start at element k * A of root
+// t's rows; its noise and its results are row t * N + k of [B, N, A] arrays.
+template <bool F16>
+__global__ __launch_bounds__(kWave) void k_root_glue_joint(const void *logits, long long row_stride, int N, int A,
+                                                           const int *legal, long long legal_stride,
+                                                           const float *noise_in, double one_minus_eps, double eps,
+                                                           int use_pow, float tau_inv, float *probs, float *beta,
+                                                           float *noise_out, const unsigned short *hexp) {
+    __shared__ float lds[kWave];
+    __shared__ float acc[9];
+    const int t = (int)(blockIdx.x / (unsigned)N), k = (int)(blockIdx.x % (unsigned)N);
+    root_glue_row<F16>(logits, row_stride, (long long)k * A, A, legal, legal_stride, (long long)k * A, noise_in,
+                       one_minus_eps, eps, use_pow, tau_inv, probs, beta, noise_out, hexp, t, (long long)blockIdx.x,
+                       threadIdx.x, lds, acc);
 }
 
 // mcts_sampled.py:116-147 for root blockIdx.x: previous agents from `factor`, the current agent
@@ -323,7 +382,7 @@ __global__ __launch_bounds__(kWave) void k_policy_glue_later(const void *logits,
     const int l = threadIdx.x;
     const int j = (int)blockIdx.y + 1 - glue;
     if (j == 0) {
-        policy_glue_row<F16>(logits, row_stride, (long long)cur * A, A, use_pow, tau_inv, probs, beta, hexp, t, l,
+        policy_glue_row<F16>(logits, row_stride, (long long)cur * A, A, use_pow, tau_inv, probs, beta, hexp, t, t, l,
                              lds, acc);
         return;
     }
@@ -1151,6 +1210,82 @@ int mz_joint_action_cached(mz_batch *b, const int32_t *later_pool, int slots, co
                        dim3(kCachedLanes), 0, stream, (const int *)later_pool, slots, (const int *)idx_x, B,
                        num_agents, current_agent, (const int *)factor, factor_cols, (const int *)actions,
                        (long long *)joint_out);
+    mz_internal_enqueued(b);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return mz_internal_fail(MZ_ERR_DEVICE, hipGetErrorString(e));
+    return MZ_OK;
+}
+
+// the workgroups of a joint glue launch, one per (root, agent); 0 when they do not fit a grid
+static unsigned joint_grid(int B, int num_agents) {
+    const long long n = (long long)B * num_agents;
+    return (n < 1 || n > 0x7fffffffll) ? 0u : (unsigned)n;
+}
+
+int mz_policy_glue_joint(mz_batch *b, const void *logits, int dtype, int64_t row_stride, int num_agents,
+                         double sampled_tau, float *probs_out, float *beta_out) {
+    const char *fn = "mz_policy_glue_joint";
+    int B = 0, A = 0;
+    hipStream_t stream = nullptr;
+    int rc = mz_internal_launch_info(b, &B, &A, &stream);
+    if (rc) return rc;
+    if (A > kWave)  // (one lane per action; joint trees take no more, include/mzmcts.h)
+        return glue_fail(MZ_ERR_UNSUPPORTED, fn, "action_space_size > 64");
+    if (num_agents < 1 || !joint_grid(B, num_agents)) return glue_fail(MZ_ERR_ARG, fn, "bad agent count");
+    if (!logits || !probs_out || !beta_out) return glue_fail(MZ_ERR_ARG, fn, "null buffer");
+    if (dtype != MZ_DT_F32 && dtype != MZ_DT_F16) return glue_fail(MZ_ERR_ARG, fn, "bad dtype");
+    if (row_stride < (int64_t)num_agents * A)
+        return glue_fail(MZ_ERR_ARG, fn, "logits row does not hold every agent's actions");
+    if (!(sampled_tau > 0.0)) return glue_fail(MZ_ERR_ARG, fn, "sampled_tau must be > 0");
+    const double inv = 1.0 / sampled_tau;  // as mz_policy_glue
+    const float tau_inv = (dtype == MZ_DT_F16) ? (float)(_Float16)inv : (float)inv;
+    const int use_pow = pow_mode(inv);
+    const unsigned short *hexp = half_exp_table();
+    const dim3 grid(joint_grid(B, num_agents));
+    if (dtype == MZ_DT_F16)
+        hipLaunchKernelGGL(k_policy_glue_joint<true>, grid, dim3(kWave), 0, stream, logits, (long long)row_stride,
+                           num_agents, A, use_pow, tau_inv, probs_out, beta_out, hexp);
+    else
+        hipLaunchKernelGGL(k_policy_glue_joint<false>, grid, dim3(kWave), 0, stream, logits, (long long)row_stride,
+                           num_agents, A, use_pow, tau_inv, probs_out, beta_out, hexp);
+    mz_internal_enqueued(b);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return mz_internal_fail(MZ_ERR_DEVICE, hipGetErrorString(e));
+    return MZ_OK;
+}
+
+int mz_root_glue_joint(mz_batch *b, const void *logits, int dtype, int64_t row_stride, int num_agents,
+                       const int32_t *legal, int64_t legal_stride, const float *noises, double noise_eps,
+                       double sampled_tau, float *probs_out, float *beta_out, float *noises_out) {
+    const char *fn = "mz_root_glue_joint";
+    int B = 0, A = 0;
+    hipStream_t stream = nullptr;
+    int rc = mz_internal_launch_info(b, &B, &A, &stream);
+    if (rc) return rc;
+    if (A > kWave)  // (one lane per action; joint trees take no more, include/mzmcts.h)
+        return glue_fail(MZ_ERR_UNSUPPORTED, fn, "action_space_size > 64");
+    if (num_agents < 1 || !joint_grid(B, num_agents)) return glue_fail(MZ_ERR_ARG, fn, "bad agent count");
+    if (!logits || !noises || !probs_out || !beta_out || !noises_out) return glue_fail(MZ_ERR_ARG, fn, "null buffer");
+    if (dtype != MZ_DT_F32 && dtype != MZ_DT_F16) return glue_fail(MZ_ERR_ARG, fn, "bad dtype");
+    if (row_stride < (int64_t)num_agents * A)
+        return glue_fail(MZ_ERR_ARG, fn, "logits row does not hold every agent's actions");
+    if (legal && legal_stride < (int64_t)num_agents * A)
+        return glue_fail(MZ_ERR_ARG, fn, "legal rows hold fewer than num_agents * A");
+    if (!(sampled_tau > 0.0)) return glue_fail(MZ_ERR_ARG, fn, "sampled_tau must be > 0");
+    const double inv = 1.0 / sampled_tau;  // as mz_root_glue: beta is a float32 array
+    const float tau_inv = (float)inv;
+    const int use_pow = pow_mode(inv);
+    const double ome = 1.0 - noise_eps;  // (Python float arithmetic)
+    const unsigned short *hexp = half_exp_table();
+    const dim3 grid(joint_grid(B, num_agents));
+    if (dtype == MZ_DT_F16)
+        hipLaunchKernelGGL(k_root_glue_joint<true>, grid, dim3(kWave), 0, stream, logits, (long long)row_stride,
+                           num_agents, A, (const int *)legal, (long long)legal_stride, noises, ome, noise_eps,
+                           use_pow, tau_inv, probs_out, beta_out, noises_out, hexp);
+    else
+        hipLaunchKernelGGL(k_root_glue_joint<false>, grid, dim3(kWave), 0, stream, logits, (long long)row_stride,
+                           num_agents, A, (const int *)legal, (long long)legal_stride, noises, ome, noise_eps,
+                           use_pow, tau_inv, probs_out, beta_out, noises_out, hexp);
     mz_internal_enqueued(b);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return mz_internal_fail(MZ_ERR_DEVICE, hipGetErrorString(e));

@@ -21,6 +21,10 @@ supports of 65..1024 elements; with `later_action_cache`: the `model.prediction(
 later agents' argmax is taken once per node by mz_policy_glue_later, which also does the policy glue,
 and the joint action reads it back through mz_joint_action_cached)
 
+(`batch_search_joint` is the one search over joint-action trees that the reference's evaluation loop
+calls, core/test.py:84: trees of agent_num = N, [B, N, A] tree inputs from mz_root_glue_joint and
+mz_policy_glue_joint, the selection's [B, N] actions straight into the model, no joint-action estimate)
+
 so a search has no host synchronisation between `prepare` and the final readback.  The root
 preprocessing (mcts_sampled.py:51-106) is split: the host draws from `np_random` (the Dirichlet
 noise, then the tree seed, in the reference's order) and packs the raw root inputs into one pinned
@@ -79,21 +83,23 @@ class DeviceSearchOutput(NamedTuple):
     (`degrees[i]` valid entries in row i).  `to_host()` gives the reference's SearchOutput."""
 
     value: torch.Tensor                  # f32 [B]
-    marginal_visit_count: torch.Tensor   # i32 [B, 1, A]
-    marginal_priors: torch.Tensor        # f32 [B, 1, A]
+    marginal_visit_count: torch.Tensor   # i32 [B, 1, A] ([B, N, A] from a joint search)
+    marginal_priors: torch.Tensor        # f32 [B, 1, A] ([B, N, A] from a joint search)
     degrees: torch.Tensor                # i32 [B]
-    sampled: dict                        # field -> [B, maxdeg] (i32 for actions / visit_count)
+    sampled: dict                        # field -> [B, maxdeg] (i32 for actions / visit_count; actions of a
+    #                                      joint search: [B, maxdeg * N])
     tree: object = None                  # the Tree_batch that ran the search (its stream; consumers)
 
     def to_host(self) -> SearchOutput:
         deg = self.degrees.cpu().numpy()
         host = {k: v.cpu().numpy() for k, v in self.sampled.items()}
         B = deg.shape[0]
+        N = self.marginal_visit_count.shape[1]  # the trees' agent_num (a joint search: all agents)
 
         def lists(name):
             a = host[name]
             if name == "actions":
-                return [np.ascontiguousarray(a[i, : deg[i]]).reshape(deg[i], 1) for i in range(B)]
+                return [np.ascontiguousarray(a[i, : deg[i] * N]).reshape(deg[i], N) for i in range(B)]
             return [np.ascontiguousarray(a[i, : deg[i]]) for i in range(B)]
 
         return SearchOutput(self.value.cpu().numpy(), self.marginal_visit_count.cpu().numpy(),
@@ -121,8 +127,14 @@ class _SearchLoop:
     memory (mz_reseed), so replaying the graph is a new search."""
 
     def __init__(self, tb, B, A, N, cur, hidden, dev, model, root_mode=None, wide=False, fused=None,
-                 wide_supports=False, later_slots=0):
+                 wide_supports=False, later_slots=0, joint=False):
         self.tb, self.B, self.A, self.N, self.cur, self.dev = tb, B, A, N, cur, dev
+        # joint: one search over the joint-action trees of all N agents (SampledMCTS.batch_search_joint;
+        # the handle has agent_num = N).  The tree inputs are [B, N, A], the selection returns every agent's
+        # action, so there is no current agent (cur = 0 is unused), no factor and no estimate of the later
+        # agents' actions; the glue is the _joint entry points, every agent's row in one launch.
+        self.joint_mode = bool(joint)
+        R = N if joint else 1  # rows of A actions per root in the tree's policy / beta / noise inputs
         # later_slots = S + 1 (SampledMCTS's later_action_cache; 0: off): the later agents' greedy actions
         # of every node, slot hidden_state_index_x, filled by mz_policy_glue_later when the node's state
         # is produced and read by mz_joint_action_cached instead of a prediction pass on the leaf.  The
@@ -158,7 +170,8 @@ class _SearchLoop:
         # [B, cols] like the caller's hidden state; B is the loop's root count, the driver's root_capacity
         # when it has one (the search's own hidden state may then hold fewer rows)
         self.root = hidden.new_empty((B, hidden[0].numel()))
-        self.rin = [torch.empty(n, dtype=torch.float32, device=dev) for n in (B, B, B * A, B * A, B * A)]
+        RA = R * A
+        self.rin = [torch.empty(n, dtype=torch.float32, device=dev) for n in (B, B, B * RA, B * RA, B * RA)]
         # root_mode = (logits dtype code, has legal): the root preprocessing runs on the device
         # (mz_root_glue) from one packed upload of the raw root inputs; None: the host computes the
         # prepare arguments (SampledMCTS.root_inputs)
@@ -166,10 +179,10 @@ class _SearchLoop:
         if root_mode is not None:
             dt_code, has_legal = root_mode
             ld = np.float16 if dt_code == MZ_DT_F16 else np.float32
-            secs = [("rewards", np.float32, B), ("values", np.float32, B), ("noise", np.float32, B * A)]
+            secs = [("rewards", np.float32, B), ("values", np.float32, B), ("noise", np.float32, B * RA)]
             if has_legal:
-                secs.append(("legal", np.int32, B * A))
-            secs.append(("logits", ld, B * A))
+                secs.append(("legal", np.int32, B * RA))
+            secs.append(("logits", ld, B * RA))
             off, self.sec = 0, {}
             for name, dt, n in secs:
                 self.sec[name] = (off, dt, n)
@@ -182,10 +195,10 @@ class _SearchLoop:
             tdt = {np.float32: torch.float32, np.float16: torch.float16, np.int32: torch.int32}
             self.dev_view = {k: self.raw[o:o + np.dtype(dt).itemsize * n].view(tdt[dt]) for k, (o, dt, n) in self.sec.items()}
         self.sel = (torch.empty(B, dtype=torch.int32, device=dev), torch.empty(B, dtype=torch.int32, device=dev),
-                    torch.empty(B, 1, dtype=torch.int32, device=dev))
+                    torch.empty(B, R, dtype=torch.int32, device=dev))
         self.joint = torch.empty(B, N, dtype=torch.int64, device=dev)
-        self.probs = torch.empty(B, A, dtype=torch.float32, device=dev)
-        self.beta = torch.empty(B, A, dtype=torch.float32, device=dev)
+        self.probs = torch.empty(B, RA, dtype=torch.float32, device=dev)
+        self.beta = torch.empty(B, RA, dtype=torch.float32, device=dev)
         self.fac = torch.zeros(B, max(cur, 1), dtype=torch.int32, device=dev)
         self.pool = None
         self.leaf = None
@@ -274,11 +287,18 @@ class _SearchLoop:
         if self.root_mode is not None:  # root preprocessing on the device, mcts_sampled.py:64-100
             dv = self.dev_view
             lg = dv.get("legal")
-            check(lib, self.root_glue(h, C.c_void_p(dv["logits"].data_ptr()), self.root_mode[0], A, 0,
-                                      None if lg is None else C.c_void_p(lg.data_ptr()), A,
-                                      C.c_void_p(dv["noise"].data_ptr()), float(eps), float(tau),
-                                      C.c_void_p(r[2].data_ptr()), C.c_void_p(r[3].data_ptr()),
-                                      C.c_void_p(r[4].data_ptr())), "root_glue")
+            if self.joint_mode:  # every agent's row: [B, N, A] in, [B, N, A] out
+                check(lib, lib.mz_root_glue_joint(h, C.c_void_p(dv["logits"].data_ptr()), self.root_mode[0], N * A,
+                                                  N, None if lg is None else C.c_void_p(lg.data_ptr()), N * A,
+                                                  C.c_void_p(dv["noise"].data_ptr()), float(eps), float(tau),
+                                                  C.c_void_p(r[2].data_ptr()), C.c_void_p(r[3].data_ptr()),
+                                                  C.c_void_p(r[4].data_ptr())), "root_glue_joint")
+            else:
+                check(lib, self.root_glue(h, C.c_void_p(dv["logits"].data_ptr()), self.root_mode[0], A, 0,
+                                          None if lg is None else C.c_void_p(lg.data_ptr()), A,
+                                          C.c_void_p(dv["noise"].data_ptr()), float(eps), float(tau),
+                                          C.c_void_p(r[2].data_ptr()), C.c_void_p(r[3].data_ptr()),
+                                          C.c_void_p(r[4].data_ptr())), "root_glue")
             r = [dv["rewards"], dv["values"], r[2], r[3], r[4]]
         # prepare + the first selection (the root's forced first child) in one launch
         tb.prepare_selection_device(r[0], r[1], r[2], r[3], K, eps, r[4], c2, c1, disc, out=self.sel)
@@ -320,7 +340,11 @@ class _SearchLoop:
             # later agents' actions from the leaf policy, :136-145: a prediction pass on the leaves, or
             # (later_action_cache) the selected nodes' cached actions; the checked search runs both
             ptr, dt = None, MZ_DT_F32
-            if cur + 1 < N and (checked or not cached or s == 0):
+            if self.joint_mode:
+                # the selection's [B, N] actions are the whole joint action (:123-124 on joint trees):
+                # widened into the static int64 buffer the model reads; no later agents to estimate
+                self.joint.copy_(act)
+            elif cur + 1 < N and (checked or not cached or s == 0):
                 pred_logits, _ = model.prediction(leaf)  # (s == 0: the leaf batch is the root batch)
                 pred_logits = pred_logits.contiguous()
                 ptr, dt = C.c_void_p(pred_logits.data_ptr()), _dtype_code(pred_logits)
@@ -331,7 +355,7 @@ class _SearchLoop:
                     h, C.c_void_p(self.later.data_ptr()), self.later.shape[0], C.c_void_p(self.sel[0].data_ptr()),
                     N, cur, C.c_void_p(self.fac.data_ptr()), self.fac.shape[1], C.c_void_p(act.data_ptr()),
                     C.c_void_p((self.joint_cached if checked else self.joint).data_ptr())), "joint_action_cached")
-            if checked or not cached:
+            if (checked or not cached) and not self.joint_mode:
                 check(lib, self.joint_action(h, ptr, dt, N, cur, C.c_void_p(self.fac.data_ptr()),
                                              self.fac.shape[1], C.c_void_p(act.data_ptr()),
                                              C.c_void_p(self.joint.data_ptr())), "joint_action")
@@ -371,6 +395,15 @@ class _SearchLoop:
                 self.pool[s + 1].copy_(nh)  # :164
             if cached:  # the policy glue, and the new node's later actions into its slot
                 self._later_glue(lib, h, logits, tau, s + 1)
+            elif self.joint_mode:  # all agents' logits, :156 on joint trees
+                if logits.dim() != 3 or logits.shape[1] != N or logits.shape[2] != A:
+                    raise ValueError(f"joint search: policy logits of shape {tuple(logits.shape)} for {N} agents "
+                                     f"and {A} actions")
+                logits = logits.contiguous()
+                check(lib, lib.mz_policy_glue_joint(h, C.c_void_p(logits.data_ptr()), _dtype_code(logits),
+                                                    logits.shape[1] * logits.shape[2], N, float(tau),
+                                                    C.c_void_p(self.probs.data_ptr()),
+                                                    C.c_void_p(self.beta.data_ptr())), "policy_glue_joint")
             else:
                 logits = logits.contiguous()
                 check(lib, self.policy_glue(h, C.c_void_p(logits.data_ptr()), _dtype_code(logits),
@@ -567,12 +600,16 @@ def _support_bounds(support) -> Tuple[int, int]:
 
 # the place of the root offset in the key of a handle whose offset is device state (device_root_offset)
 _DEVICE_OFFSET = "device_root_offset"
+# the place of the current agent in the key of a joint search's loop (no agent index is negative)
+_JOINT_AGENT = -1
 
 
-def skip_search_draws(config, np_random, total: int) -> None:
+def skip_search_draws(config, np_random, total: int, num_agents: int = 1) -> None:
     """What one search of `total` roots draws from `np_random` before it launches anything: the
-    Dirichlet rows, then the tree seed (mcts_sampled.py:68,89)."""
-    np_random.dirichlet([config.root_dirichlet_alpha] * config.action_space_size, int(total))
+    Dirichlet rows, then the tree seed (mcts_sampled.py:68,89).  `num_agents`: a joint search
+    (batch_search_joint) draws one row per (root, agent)."""
+    size = int(total) if int(num_agents) == 1 else (int(total), int(num_agents))
+    np_random.dirichlet([config.root_dirichlet_alpha] * config.action_space_size, size)
     np_random.choice(256)
 
 
@@ -721,23 +758,27 @@ class SampledMCTS:
     # ---------------------------------------------------------------------------------------
     def root_inputs(self, network_output, current_agent_idx, legal_actions_lst, add_noise, sampled_tau):
         """Root preprocessing, mcts_sampled.py:51-106, in numpy on the host (it draws from
-        np_random).  Returns the prepare() arguments and the tree seed."""
+        np_random).  Returns the prepare() arguments and the tree seed.  `current_agent_idx` None: the
+        joint search's (batch_search_joint), every agent's row, [B, N, A] arrays."""
         cfg = self.config
         alpha, eps = cfg.root_dirichlet_alpha, cfg.root_exploration_fraction
         A = cfg.action_space_size
         B = network_output.hidden_state.shape[0]
-        logits = _np(network_output.policy_logits)[:, current_agent_idx, :].reshape(B, 1, A)
+        joint = current_agent_idx is None
+        logits = _np(network_output.policy_logits)
+        R = logits.shape[1] if joint else 1
+        logits = logits.reshape(B, R, A) if joint else logits[:, current_agent_idx, :].reshape(B, 1, A)
         # softmax in the logits' own dtype (float16 under autocast), :64-65
         probs = np.exp(logits - np.max(logits, axis=-1, keepdims=True))
         probs = probs / np.sum(probs, axis=-1, keepdims=True)
         # Dirichlet noise is always drawn, then disabled for evaluation, :68-70
-        noises = self.draw_rows(lambda n: self.np_random.dirichlet([alpha] * A, n), B)
-        noises = noises.astype(np.float32).reshape(B, 1, A)
+        noises = self.draw_rows(lambda n: self.np_random.dirichlet([alpha] * A, (n, R) if joint else n), B)
+        noises = noises.astype(np.float32).reshape(B, R, A)
         if not add_noise:
             eps = 0.0
         mask = None
         if legal_actions_lst is not None:  # :73-83
-            mask = legal_actions_lst[:, current_agent_idx, :].reshape(B, 1, A)
+            mask = (legal_actions_lst if joint else legal_actions_lst[:, current_agent_idx, :]).reshape(B, R, A)
             probs *= mask
             probs += mask * 1e-4
             probs = probs / np.sum(probs, axis=-1, keepdims=True)
@@ -759,33 +800,38 @@ class SampledMCTS:
         """The raw root inputs of the device root preprocessing (mz_root_glue): the Dirichlet draws
         (np_random, then the tree seed, in the reference's order, mcts_sampled.py:68,89) and the
         arrays to upload, or None when the device path does not cover the inputs' dtypes (the host
-        path, root_inputs, takes them).  Returns (arrays, (logits dtype code, has legal), eps, seed)."""
+        path, root_inputs, takes them).  Returns (arrays, (logits dtype code, has legal), eps, seed).
+        `current_agent_idx` None: the joint search's (batch_search_joint), every agent's columns and one
+        Dirichlet row per (root, agent), for mz_root_glue_joint."""
         cfg = self.config
         A = cfg.action_space_size
         B = network_output.hidden_state.shape[0]
+        joint = current_agent_idx is None
         lg = network_output.policy_logits
         if isinstance(lg, torch.Tensor):
             if not lg.is_cuda or lg.dtype not in (torch.float32, torch.float16):
                 return None
-            logits = lg[:, current_agent_idx, :]
+            logits = lg if joint else lg[:, current_agent_idx, :]
             code = _dtype_code(lg)
         else:
             lg = np.asarray(lg)
             if lg.dtype not in (np.float32, np.float16):
                 return None
-            logits = lg[:, current_agent_idx, :]
+            logits = lg if joint else lg[:, current_agent_idx, :]
             code = MZ_DT_F16 if lg.dtype == np.float16 else MZ_DT_F32
+        R = lg.shape[1] if joint else 1
         legal = None
         if legal_actions_lst is not None:
             la = _np(legal_actions_lst)
             if la.dtype.kind not in "iub":
                 return None  # (float masks: numpy's float arithmetic differs; the host path)
-            legal = la[:, current_agent_idx, :]
+            legal = la if joint else la[:, current_agent_idx, :]
             if legal.dtype.kind != "b" and legal.size and (legal.min() < -(1 << 31) or legal.max() >= (1 << 31)):
                 return None
             legal = legal.astype(np.int32)
         alpha, eps = cfg.root_dirichlet_alpha, cfg.root_exploration_fraction
-        noise = self.draw_rows(lambda n: self.np_random.dirichlet([alpha] * A, n), B).astype(np.float32)
+        noise = self.draw_rows(lambda n: self.np_random.dirichlet([alpha] * A, (n, R) if joint else n),
+                               B).astype(np.float32)
         if not add_noise:
             eps = 0.0
         seed = self.np_random.choice(256)  # drawn after the noise, :89
@@ -805,30 +851,34 @@ class SampledMCTS:
             raise ValueError(f"batch of {B} roots but the root shard is [{lo}, {hi})")
         return draw(total)[lo:hi]
 
-    def skip_search(self) -> None:
+    def skip_search(self, num_agents: int = 1) -> None:
         """Consume from `np_random` exactly what one search consumes -- the Dirichlet rows of the whole
         batch, then the tree seed (mcts_sampled.py:68,89) -- and launch nothing: the search of an empty
-        root shard (`device_root_offset`), which keeps this rank's generator in step with the others'."""
+        root shard (`device_root_offset`), which keeps this rank's generator in step with the others'.
+        `num_agents`: the model's agent count where the other ranks run batch_search_joint."""
         if self.root_shard is None or self.root_shard[0] != self.root_shard[1]:
             raise ValueError(f"skip_search: root shard {self.root_shard} is not empty")
-        skip_search_draws(self.config, self.np_random, self.root_shard[2])
+        skip_search_draws(self.config, self.np_random, self.root_shard[2], num_agents)
 
     def draw_root_uniforms(self, B: int) -> np.ndarray:
         """One double per root in root order, as B np_random.choice(n, p) calls draw them."""
         return np.asarray(self.draw_rows(lambda n: self.np_random.random(n), B), dtype=np.float64)
 
-    def _tree(self, B, seed, device):
+    def _tree(self, B, seed, device, agent_num: int = 1):
+        """The cached handle of this geometry, reseeded.  `agent_num` > 1: joint-action trees
+        (batch_search_joint); what the handle refuses (A > 64, K > 64, N * A > 4096) raises here."""
         cfg = self.config
         # (pb_c_base, pb_c_init) select the handle's pUCT tables, which a graph replay does not
         # rewrite: a handle serves one pair only
         key = (threading.get_ident(), B, cfg.action_space_size, cfg.sampled_action_times, cfg.num_simulations,
                float(cfg.tree_value_stat_delta_lb), float(cfg.mcts_rho), float(cfg.mcts_lambda),
                float(cfg.pb_c_base), float(cfg.pb_c_init), str(device), id(self._lib),
-               _DEVICE_OFFSET if self.device_root_offset else self._root_offset())
+               _DEVICE_OFFSET if self.device_root_offset else self._root_offset(), int(agent_num))
         with _LOCK:
             tb = _TREES.get(key)
             if tb is None:
-                tb = Tree_batch(B, 1, cfg.action_space_size, cfg.sampled_action_times, cfg.num_simulations,
+                tb = Tree_batch(B, int(agent_num), cfg.action_space_size, cfg.sampled_action_times,
+                                cfg.num_simulations,
                                 cfg.tree_value_stat_delta_lb, int(seed), cfg.mcts_rho, cfg.mcts_lambda,
                                 root_offset=0 if self.device_root_offset else self._root_offset(),
                                 lib=self._lib)
@@ -860,7 +910,7 @@ class SampledMCTS:
 
     def batch_search_device(self, model, network_output, current_agent_idx: int, factor, true_num_agents: int,
                             legal_actions_lst=None, device=None, add_noise: bool = False, sampled_tau: float = 1.0,
-                            sampled_actions_res=None, _host_readback: bool = False):
+                            sampled_actions_res=None, _host_readback: bool = False, _joint: bool = False):
         """The search with device-resident outputs (DeviceSearchOutput), for on-device consumers."""
         if sampled_actions_res is not None:
             raise NotImplementedError  # as the reference, mcts_sampled.py:108-109
@@ -868,6 +918,9 @@ class SampledMCTS:
         c2, c1, disc = cfg.pb_c_base, cfg.pb_c_init, cfg.discount
         A, K, S = cfg.action_space_size, cfg.sampled_action_times, cfg.num_simulations
         N, cur = int(true_num_agents), int(current_agent_idx)
+        # a joint search (batch_search_joint_device): no current agent; None selects every agent's root
+        # inputs, and _JOINT_AGENT stands in the loop's key where a per-agent loop has its agent
+        root_agent, cur = (None, 0) if _joint else (cur, cur)
         hidden = network_output.hidden_state
         if not (isinstance(hidden, torch.Tensor) and hidden.is_cuda):
             raise ValueError("network_output.hidden_state must be a GPU tensor")
@@ -880,17 +933,18 @@ class SampledMCTS:
         if B < 1:
             raise ValueError("batch of 0 roots: an empty root shard searches nothing (skip_search)")
 
-        raw = self.root_raw(network_output, cur, legal_actions_lst, add_noise) if self.device_root else None
+        raw = self.root_raw(network_output, root_agent, legal_actions_lst, add_noise) if self.device_root else None
         if raw is not None:
             root_arrays, root_mode, eps, seed = raw
         else:
-            (rr, rv, rp, rb, eps, rn), seed = self.root_inputs(network_output, cur, legal_actions_lst, add_noise,
-                                                               sampled_tau)
+            (rr, rv, rp, rb, eps, rn), seed = self.root_inputs(network_output, root_agent, legal_actions_lst,
+                                                               add_noise, sampled_tau)
             root_arrays, root_mode = (rr, rv, rp, rb, rn), None
         with torch.cuda.device(dev):
-            tb = self._tree(Bc, seed, dev)
+            tb = self._tree(Bc, seed, dev, N if _joint else 1)
             # the discount is a kernel argument of the recorded launches
-            key = (threading.get_ident(), id(tb), id(model), N, cur, float(eps), float(sampled_tau), float(disc),
+            key = (threading.get_ident(), id(tb), id(model), N, _JOINT_AGENT if _joint else cur, float(eps),
+                   float(sampled_tau), float(disc),
                    (Bc,) + tuple(hidden.shape[1:]), hidden.dtype, root_mode, self.wide_actions, self.fused_transforms,
                    self.wide_supports, self.later_action_cache)
             with _LOCK:
@@ -904,7 +958,8 @@ class SampledMCTS:
                     st = _LOOPS[key] = _SearchLoop(tb, Bc, A, N, cur, hidden, dev, model, root_mode,
                                                    wide=self.wide_actions, fused=self.fused_transforms,
                                                    wide_supports=self.wide_supports,
-                                                   later_slots=S + 1 if self.later_action_cache else 0)
+                                                   later_slots=S + 1 if self.later_action_cache else 0,
+                                                   joint=_joint)
                     st.storage = sig
                 _LOOPS.move_to_end(key)
                 while len(_LOOPS) > max(_MAX_LOOPS, 1):  # least recently used first
@@ -947,6 +1002,53 @@ class SampledMCTS:
             tb.get_roots_device(disc, values=value, marginal_visit_count=mv, marginal_priors=mp, degrees=deg,
                                 sampled=sampled)
             return DeviceSearchOutput(value, mv, mp, deg, sampled, tb)
+
+    # ---------------------------------------------------------------------------------------
+    def batch_search_joint(self, model, network_output, legal_actions_lst: np.ndarray = None,
+                           device: torch.device = None, add_noise: bool = False, sampled_tau: float = 1.0,
+                           sampled_actions_res: Tuple[np.ndarray, np.ndarray] = None) -> SearchOutput:
+        """One search over the joint-action trees of all agents: the call of the reference's evaluation
+        loop, `SampledMCTS(config, np_random).batch_search(model, network_output, legal_actions_lst,
+        device, False, 1.0)` (core/test.py:84), whose `roots_sampled_actions[i][action_pos]` is the whole
+        joint action (:101-107).
+
+        It is mcts_sampled.py:34-200 with num_agents = N, the model's agent count
+        (`network_output.policy_logits.shape[1]`), in place of 1 (:53,89): the root policy, the Dirichlet
+        noise ((B, N) rows, drawn before the tree seed as :68,89), the legal mask and beta are [B, N, A];
+        every node samples K joint actions; the selection returns all N agents' actions (:123-124), so
+        there is no factor, no prediction pass for later agents (:116-121, :136-147 go) and
+        `recurrent_inference(leaf, batch_actions)` takes them as they are; the policy glue of every
+        simulation covers all agents' logits (:156).  In the result `marginal_*` are [B, N, A] and
+        `sampled_actions[i]` is (K_i, N).  With N = 1 the trees, the kernels and the results are those of
+        `batch_search(model, network_output, 0, None, 1, ...)`.
+
+        On the device: one packed upload of the raw root inputs, mz_root_glue_joint, then per simulation
+        the selection's [B, N] actions widened into the model's int64 action buffer, the model, and
+        mz_policy_glue_joint, around the fused tree kernel; the first search is eager, later ones replay
+        one recorded graph.  `fused_transforms`, `wide_supports` and `root_shard` compose;
+        `root_capacity`, `later_action_cache` and `wide_actions` raise ValueError.  What the tree handle
+        refuses for N > 1 (A > 64, K > 64, N * A > 4096) raises from Tree_batch before anything launches."""
+        return self.batch_search_joint_device(model, network_output, legal_actions_lst, device, add_noise,
+                                              sampled_tau, sampled_actions_res, _host_readback=True)
+
+    def batch_search_joint_device(self, model, network_output, legal_actions_lst=None, device=None,
+                                  add_noise: bool = False, sampled_tau: float = 1.0, sampled_actions_res=None,
+                                  _host_readback: bool = False):
+        """batch_search_joint with device-resident outputs (DeviceSearchOutput; consume.select_joint_actions
+        takes the joint actions from it)."""
+        for flag, on in (("root_capacity", self.root_capacity is not None),
+                         ("later_action_cache", self.later_action_cache), ("wide_actions", self.wide_actions)):
+            if on:
+                raise ValueError(f"batch_search_joint does not take {flag}: " + {
+                    "root_capacity": "the padded loop is the per-agent one",
+                    "later_action_cache": "a joint search estimates no later agents' actions",
+                    "wide_actions": "joint-action trees take at most 64 actions per agent"}[flag])
+        logits = network_output.policy_logits
+        if getattr(logits, "ndim", 0) != 3:
+            raise ValueError("network_output.policy_logits must be [B, num_agents, A]")
+        return self.batch_search_device(model, network_output, 0, None, int(logits.shape[1]), legal_actions_lst,
+                                        device, add_noise, sampled_tau, sampled_actions_res,
+                                        _host_readback=_host_readback, _joint=True)
 
     @staticmethod
     def _recurrent(model, hidden, action):
