@@ -145,15 +145,16 @@ int mz_joint_action(mz_batch *b, const void *pred_logits, int dtype, int num_age
 /* Action spaces past 64 (the handle takes up to 255): mz_policy_glue_wide, mz_root_glue_wide and
  * mz_joint_action_wide have the signatures, argument checks and results of mz_policy_glue,
  * mz_root_glue and mz_joint_action and accept any action_space_size the handle has (1..255).
- *   A <= 64: they launch the same kernels as the narrow entry points (one lane per action), so the
+ * Both sets launch the same kernels, templated on the tile count ceil(A / 64): one wave per root, lane
+ * l holds the actions l + 64 j, j < ceil(A / 64).
+ *   A <= 64: one tile, one lane per action: the instantiation the narrow entry points launch, so the
  *     results are identical by construction.
- *   A  > 64: one wave per root still; lane l holds the actions l + 64 j, j < ceil(A / 64).  The
- *     elementwise arithmetic is unchanged.  np.sum of a row of n > 128 elements follows numpy's
+ *   A  > 64: the same row code over 2 to 4 tiles.  np.sum of a row of n > 128 elements follows numpy's
  *     pairwise recursion (n2 = n / 2, n2 -= n2 % 8; sum(a, n2) + sum(a + n2, n - n2)): at most three
  *     base-case blocks for n <= 255, joined as s0 + s1 or s0 + (s1 + s2).  np.max is the row's NaN
- *     when it holds one (its first in action order), and the softmax of such a row is that NaN in
- *     every element, sign and payload as numpy on x86-64 leaves them; np.argmax is the smallest
- *     action holding a NaN, else the smallest action equal to the maximum.
+ *     when it holds one (its first in action order); the policy glue's NaN rows are as described at
+ *     mz_policy_glue, the root glue's softmax of such a row is that NaN in every element; np.argmax
+ *     is the smallest action holding a NaN, else the smallest action equal to the maximum.
  * The narrow entry points keep refusing A > 64 (MZ_ERR_UNSUPPORTED, "action_space_size > 64"): two
  * tests pin that refusal (tests/test_gpu_parity.py, tests/test_driver.py), so the wide path is a
  * separate set of entry points that a driver opts into (mazero_amd.mcts_sampled, wide_actions). */
@@ -181,8 +182,8 @@ int mz_joint_action_wide(mz_batch *b, const void *pred_logits, int dtype, int nu
  * later_out: int32 [B, num_agents]; column k > current_agent receives np.argmax(logits[i, k, :]) (first
  * maximum, first NaN wins, as mz_joint_action); columns <= current_agent are not written.  May be NULL
  * when current_agent == num_agents - 1: the call then equals mz_policy_glue.
- * Any action_space_size the handle has (1..255): one lane per action up to 64, the tiles of the _wide
- * entry points above.  Nothing is allocated or uploaded, so the call can be captured in a graph. */
+ * Any action_space_size the handle has (1..255): the tiles of the entry points above.  Nothing is
+ * allocated or uploaded, so the call can be captured in a graph. */
 int mz_policy_glue_later(mz_batch *b, const void *logits, int dtype, int64_t row_stride, int num_agents,
                          int current_agent, double sampled_tau, float *probs_out, float *beta_out,
                          int32_t *later_out);
@@ -203,11 +204,11 @@ int mz_joint_action_cached(mz_batch *b, const int32_t *later_pool, int slots, co
 
 /* The glue of a joint search (a handle of agent_num = N > 1, whose prepare and expansion take
  * [B, N, A] policy, beta and noise): every agent's row in one launch, one wave per (root, agent).
- * The row code is that of mz_policy_glue / mz_root_glue, so for every agent k the slice [:, k, :] of an
- * output holds the bytes of the narrow call with col_offset = k * A on the agent's own columns.
- * Nothing is allocated or uploaded, so the calls can be captured in a graph.  action_space_size > 64 is
- * MZ_ERR_UNSUPPORTED (one lane per action; joint trees take no more); num_agents need not be the
- * handle's agent_num (the handle gives B, A and the stream).
+ * The kernel is that of mz_policy_glue / mz_root_glue with an agent per grid row, so for every agent k
+ * the slice [:, k, :] of an output holds the bytes of the narrow call with col_offset = k * A on the
+ * agent's own columns.  Nothing is allocated or uploaded, so the calls can be captured in a graph.
+ * action_space_size > 64 is MZ_ERR_UNSUPPORTED (joint trees take no more); num_agents (1..65535, the
+ * grid's rows) need not be the handle's agent_num (the handle gives B, A and the stream).
  *
  * mz_policy_glue_joint: logits [B, num_agents, A] of dtype `dtype`, row stride `row_stride` >=
  * num_agents * A elements; probs_out, beta_out float32 [B, num_agents, A].
@@ -267,8 +268,9 @@ int mz_inverse_transform_wide(mz_batch *b, void *stream, int stage, int n,
  * row.  Host only, no device call; for the tests that pin it against ReduceConfig's rule. */
 int mz_inverse_sum_plan(int S, int n, int *vectorized, int *block_width);
 
-/* The base-case blocks the wide kernels sum a row of n elements in (1 <= n <= 255), as the launchers
- * compute them: starts[3], lens[3] (unused entries 0) and their count.  Host only, no device call;
+/* The base-case blocks the glue kernels sum a row of n elements in (1 <= n <= 255; every width, the
+ * one block (0, n) up to n = 128), from the function the kernels compute them with: starts[3], lens[3]
+ * (unused entries 0) and their count.  Host only, no device call;
  * for the tests that check the plan against np.sum. */
 int mz_wide_sum_plan(int n, int32_t *starts, int32_t *lens, int32_t *num_blocks);
 

@@ -22,6 +22,7 @@
 #include <cstdlib>
 #include <mutex>
 #include <string>
+#include <type_traits>
 
 #include "../../include/mzdriver.h"
 #include "mz_internal.h"
@@ -91,34 +92,6 @@ __device__ __forceinline__ float load_elem(const void *p, long long i) {
     return static_cast<const float *>(p)[i];
 }
 
-// numpy pairwise-sum base case over lds[0..n), n <= 128; result broadcast to every lane.
-__device__ float np_row_sum(float v, int l, int n, float *lds, float *acc) {
-    if (l < n) lds[l] = v;
-    __syncthreads();
-    if (n >= 8 && l < 8) {
-        const int n8 = n - n % 8;
-        float r = lds[l];
-        for (int i = 8; i < n8; i += 8) r += lds[i + l];
-        acc[l] = r;
-    }
-    __syncthreads();
-    if (l == 0) {
-        float res;
-        if (n < 8) {
-            res = 0.f;
-            for (int i = 0; i < n; ++i) res += lds[i];
-        } else {
-            res = ((acc[0] + acc[1]) + (acc[2] + acc[3])) + ((acc[4] + acc[5]) + (acc[6] + acc[7]));
-            for (int i = n - n % 8; i < n; ++i) res += lds[i];
-        }
-        acc[8] = res;
-    }
-    __syncthreads();
-    const float out = acc[8];
-    __syncthreads();
-    return out;
-}
-
 __device__ __forceinline__ float wave_max(float v) {
     for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, kWave));
     return v;
@@ -155,70 +128,6 @@ int pow_mode(double inv) {
 template <bool F16>
 __device__ __forceinline__ float np_softmax_nan(bool nan_any) {
     return __uint_as_float((F16 && !nan_any) ? 0xffc00000u : 0x7fc00000u);
-}
-
-// mcts_sampled.py:158-161 (+ .astype(np.float32), :169-170) for root t, lane l of its wave: the body
-// of k_policy_glue, of role 0 of k_policy_glue_later and of k_policy_glue_joint (lds[kWave] and acc[9]
-// are the workgroup's).  The A results go to row `out_row` of probs / beta.
-template <bool F16>
-__device__ __forceinline__ void policy_glue_row(const void *logits, long long row_stride, long long col_off, int A,
-                                                int use_pow, float tau_inv, float *probs, float *beta,
-                                                const unsigned short *hexp, int t, long long out_row, int l,
-                                                float *lds, float *acc) {
-    const bool on = l < A;
-    const float x = on ? load_elem<F16>(logits, (long long)t * row_stride + col_off + l) : -INFINITY;
-    // np.max(..., axis=-1): NaN propagates
-    const bool nan_any = __ballot(on && (x != x)) != 0;
-    const float m = nan_any ? NAN : wave_max(on ? x : -INFINITY);
-    const float d = round_as<F16>(x - m);
-    const float e = np_exp_as<F16>(d, hexp);
-    const float s = round_as<F16>(np_row_sum(e, l, A, lds, acc));
-    const float p = round_as<F16>(e / s);
-    // `** (1 / sampled_tau)`: numpy returns the array itself for an exponent of 1.0
-    const float q = use_pow ? np_pow_as<F16>(p, tau_inv, use_pow) : p;
-    const float s2 = round_as<F16>(np_row_sum(q, l, A, lds, acc));
-    const float b = round_as<F16>(q / s2);
-    const bool nan_row = s != s;  // (the sum is every lane's: the whole row)
-    if (on) {
-        probs[out_row * A + l] = nan_row ? np_softmax_nan<F16>(nan_any) : p;
-        beta[out_row * A + l] = nan_row ? np_softmax_nan<F16>(nan_any) : b;
-    }
-}
-
-template <bool F16>
-__global__ __launch_bounds__(kWave) void k_policy_glue(const void *logits, long long row_stride, long long col_off,
-                                                       int A, int use_pow, float tau_inv, float *probs,
-                                                       float *beta, const unsigned short *hexp) {
-    __shared__ float lds[kWave];
-    __shared__ float acc[9];
-    policy_glue_row<F16>(logits, row_stride, col_off, A, use_pow, tau_inv, probs, beta, hexp, blockIdx.x,
-                         blockIdx.x, threadIdx.x, lds, acc);
-}
-
-// mz_policy_glue_joint: k_policy_glue for every agent of a joint search in one launch, one wave per
-// (root, agent), workgroup t * N + k.  Agent k's logits start at element k * A of root t's row and its
-// results are row t * N + k of the [B, N, A] outputs: the row code is k_policy_glue's own.
-template <bool F16>
-__global__ __launch_bounds__(kWave) void k_policy_glue_joint(const void *logits, long long row_stride, int N, int A,
-                                                             int use_pow, float tau_inv, float *probs, float *beta,
-                                                             const unsigned short *hexp) {
-    __shared__ float lds[kWave];
-    __shared__ float acc[9];
-    const int t = (int)(blockIdx.x / (unsigned)N), k = (int)(blockIdx.x % (unsigned)N);
-    policy_glue_row<F16>(logits, row_stride, (long long)k * A, A, use_pow, tau_inv, probs, beta, hexp, t,
-                         (long long)blockIdx.x, threadIdx.x, lds, acc);
-}
-
-// np.argmax of the row of A <= 64 elements that starts at element `row` (mcts_sampled.py:136-145): the
-// first NaN if the row holds one, else the first maximum; the result in every lane of the wave.
-template <bool F16>
-__device__ __forceinline__ int np_argmax_row(const void *p, long long row, int A, int l) {
-    const bool on = l < A;
-    const float v = on ? load_elem<F16>(p, row + l) : -INFINITY;
-    const unsigned long long nan_mask = __ballot(on && (v != v));
-    if (nan_mask) return __ffsll((long long)nan_mask) - 1;  // (wave-uniform)
-    const float m = wave_max(v);
-    return __ffsll((long long)__ballot(on && v == m)) - 1;
 }
 
 // float64 -> float16 with one rounding (round to nearest, ties to even), as numpy casts a float64
@@ -264,96 +173,299 @@ __device__ __forceinline__ float store_d(double v) {
     return (float)v;
 }
 
-// Root preprocessing of mcts_sampled.py:64-100 for root blockIdx.x (prepare's policy, beta and noise
-// arguments, :102-106), with numpy 2.x's dtype rules (NEP 50):
+// ------------------------------------------------------------------------------------------------
+// One wave per row of A <= 255 actions: lane l holds the actions l + 64 j, j < T = ceil(A / 64), in
+// registers (T is a template parameter: the tile loops unroll; T = 1 is one lane per action).  The
+// row reductions and row bodies below are stated once for every T.
+//
+// np.sum(axis=-1) of a row of n > 128 elements is no longer one base case: numpy's pairwise sum
+// splits at n2 = n / 2, n2 -= n2 % 8 and adds pairwise(a, n2) + pairwise(a + n2, n - n2),
+// recursively.  For n <= 255 the first half (<= 120) is always a base case and the second (<= 135)
+// splits at most once more, so a row is at most three base-case blocks, each starting at a multiple
+// of 8, joined from the right: s0, s0 + s1 or s0 + (s1 + s2); a row of n <= 128 is the one block
+// (0, n).  The launcher walks the recursion once (sum_plan) and hands the kernel the blocks.
+constexpr int kWideMax = 255;       // the handle's own limit (a node packs its action in 8 bits)
+constexpr int kPairwiseBlock = 128; // numpy's PW_BLOCKSIZE
+constexpr int kMaxBlocks = 3;
+
+// the base-case blocks of numpy's pairwise sum over n elements, 1 <= n <= 255, in row order: byte b is
+// the length of block b (1..128; 0: no such block), and a block starts where the one before it ends.
+// (Past 257 elements a left half would split too, and the join would no longer be the right-nested one.)
+unsigned sum_plan(int n) {
+    unsigned lens = 0u;
+    int shift = 0;
+    while (n > kPairwiseBlock) {  // pairwise(a, n2) + pairwise(a + n2, n - n2): n2 <= 120 is a base case
+        int n2 = n / 2;
+        n2 -= n2 % 8;
+        lens |= (unsigned)n2 << shift;
+        n -= n2;
+        shift += 8;
+    }
+    return lens | (unsigned)n << shift;
+}
+
+// The kernels take the plan in place of A, which it holds: one block (A itself) for one tile, else the
+// lengths' sum.
+template <int T>
+__device__ __forceinline__ int plan_len(unsigned plan) {
+    if constexpr (T == 1) return (int)plan;
+    return (int)((plan & 0xffu) + (plan >> 8 & 0xffu) + (plan >> 16));
+}
+
+// v of another lane of the same row of 16 lanes, by a DPP control (no LDS round trip as __shfl_xor's):
+// lane l ^ 1, lane l ^ 2, and lane l ^ 7 (the other quad of l's group of 8)
+constexpr int kDppXor1 = 0xb1, kDppXor2 = 0x4e, kDppHalfMirror = 0x141;  // quad_perm [1,0,3,2], [2,3,0,1]
+template <int kCtrl>
+__device__ __forceinline__ float lane_dpp(float v) {
+    return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), kCtrl, 0xf, 0xf, true));
+}
+
+// lane `lane`'s v (a constant lane) in every lane
+__device__ __forceinline__ float lane_value(float v, int lane) {
+    return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), lane));
+}
+
+// np.sum over the row whose element l + 64 j is v[j] (lds[64 T] is the workgroup's; plan = sum_plan(A));
+// result in every lane.  Lanes 8 b + i run accumulator i of block b; the 8 accumulators combine as a
+// butterfly, which is numpy's ((r0+r1)+(r2+r3))+((r4+r5)+(r6+r7)) in every lane of the group (float
+// addition commutes; after two steps a quad's lanes agree, so any lane of the other quad serves the
+// third); lane 8 b adds the block's n % 8 tail; the block sums join from the right.  A block of fewer
+// than 8 elements (the row itself, A < 8) is numpy's sequential sum from 0.0f: its lanes load no
+// accumulator, so the butterfly leaves 0.0f and the tail adds elements 0 .. len - 1 in order.
+// With one tile the row is the one block (0, A), which the plan says too: stated in place, the compiler
+// sees the block's bounds and keeps the short loop short (measured: profiles/glue_unify/README.md).
+// Every lane of the wave is active here: the callers' control flow is workgroup-uniform.
+template <int T>
+__device__ float np_row_sum(const float (&v)[T], int l, int A, unsigned plan, float *lds) {
+#pragma unroll
+    for (int j = 0; j < T; ++j)
+        if (l + kWave * j < A) lds[l + kWave * j] = v[j];
+    __syncthreads();
+    const int blk = l >> 3, i = l & 7;
+    int start = 0, len = blk == 0 ? A : 0;
+    if constexpr (T > 1) {
+        const int len0 = (int)(plan & 0xffu), len1 = (int)(plan >> 8 & 0xffu);
+        start = blk == 0 ? 0 : blk == 1 ? len0 : len0 + len1;
+        len = blk < kMaxBlocks ? (int)(plan >> (8 * blk) & 0xffu) : 0;
+    }
+    // (lanes past the last block idle with len = 0)
+    const int n8 = len - len % 8;
+    float r = 0.f;
+    if (len >= 8) {  // (the row holds lds[start + i] only for i < len)
+        r = lds[start + i];
+        for (int k = 8; k < n8; k += 8) r += lds[start + k + i];
+    }
+    r += lane_dpp<kDppXor1>(r);
+    r += lane_dpp<kDppXor2>(r);
+    r += lane_dpp<kDppHalfMirror>(r);
+    if (i == 0)
+        for (int k = n8; k < len; ++k) r += lds[start + k];
+    float s = lane_value(r, 0);
+    if constexpr (T > 1) {
+        const float s1 = lane_value(r, 8), s2 = lane_value(r, 16);
+        if (plan >> 16)
+            s = s + (s1 + s2);
+        else if (plan >> 8)
+            s = s + s1;
+    }
+    __syncthreads();  // (the row is read: the next sum may overwrite it)
+    return s;
+}
+
+// np.max(axis=-1) of the row: a NaN anywhere makes it that NaN (one ballot per tile; the first in
+// action order where the row holds several)
+template <int T>
+__device__ __forceinline__ float np_row_max(const float (&x)[T], int l, int A) {
+    bool nan_any = false;
+    float m = -INFINITY, nan_v = 0.f;
+#pragma unroll
+    for (int j = 0; j < T; ++j) {
+        const bool on = l + kWave * j < A;
+        const unsigned long long nan_mask = __ballot(on && (x[j] != x[j]));
+        if (!nan_any && nan_mask) {  // (wave-uniform)
+            nan_any = true;
+            nan_v = __shfl(x[j], __ffsll((long long)nan_mask) - 1, kWave);
+        }
+        m = fmaxf(m, on ? x[j] : -INFINITY);
+    }
+    return nan_any ? nan_v : wave_max(m);
+}
+
+// np.argmax of the row of A elements that starts at element `row` of p (mcts_sampled.py:136-145): the
+// smallest action holding a NaN if there is one, else the smallest action equal to the maximum; the
+// result in every lane.  Action l + 64 j orders by tile first, so the tiles are scanned in order and
+// the first set ballot bit taken inside a tile.
+template <bool F16, int T>
+__device__ __forceinline__ int np_argmax_row(const void *p, long long row, int A, int l) {
+    float v[T];
+    float m = -INFINITY;
+    int idx = -1;
+#pragma unroll
+    for (int j = 0; j < T; ++j) {
+        const int a = l + kWave * j;
+        const bool on = a < A;
+        v[j] = on ? load_elem<F16>(p, row + a) : -INFINITY;
+        m = fmaxf(m, v[j]);
+        const unsigned long long nan_mask = __ballot(on && (v[j] != v[j]));
+        if (idx < 0 && nan_mask) idx = kWave * j + __ffsll((long long)nan_mask) - 1;
+    }
+    if (idx < 0) {  // (wave-uniform)
+        m = wave_max(m);
+#pragma unroll
+        for (int j = 0; j < T; ++j) {
+            const unsigned long long hit = __ballot(l + kWave * j < A && v[j] == m);
+            if (idx < 0 && hit) idx = kWave * j + __ffsll((long long)hit) - 1;
+        }
+    }
+    return idx;
+}
+
+// mcts_sampled.py:158-161 (+ .astype(np.float32), :169-170) for root t, lane l of its wave: the body
+// of k_policy_glue and of role 0 of k_policy_glue_later.  The agent's logits start at element col_off
+// of the root's row; the A results go to row `out_row` of probs / beta.  A row that holds a NaN, or
+// whose maximum is infinite, sums to a NaN and is set by hand (np_softmax_nan), so the GPU's own
+// x - max is good enough in front of it.
+template <bool F16, int T>
+__device__ __forceinline__ void policy_glue_row(const void *logits, long long row_stride, long long col_off, int A,
+                                                unsigned plan, int use_pow, float tau_inv, float *probs,
+                                                float *beta, const unsigned short *hexp, int t,
+                                                long long out_row, int l, float *lds) {
+    float x[T], e[T], p[T], q[T];
+#pragma unroll
+    for (int j = 0; j < T; ++j) {
+        const int a = l + kWave * j;
+        x[j] = a < A ? load_elem<F16>(logits, (long long)t * row_stride + col_off + a) : -INFINITY;
+    }
+    const float m = np_row_max<T>(x, l, A);
+    const bool nan_any = m != m;
+#pragma unroll
+    for (int j = 0; j < T; ++j) e[j] = np_exp_as<F16>(round_as<F16>(x[j] - m), hexp);
+    const float s = round_as<F16>(np_row_sum<T>(e, l, A, plan, lds));
+#pragma unroll
+    for (int j = 0; j < T; ++j) {
+        p[j] = round_as<F16>(e[j] / s);
+        // `** (1 / sampled_tau)`: numpy returns the array itself for an exponent of 1.0
+        q[j] = use_pow ? np_pow_as<F16>(p[j], tau_inv, use_pow) : p[j];
+    }
+    const float s2 = round_as<F16>(np_row_sum<T>(q, l, A, plan, lds));
+    const bool nan_row = s != s;  // (the sum is every lane's: the whole row)
+#pragma unroll
+    for (int j = 0; j < T; ++j) {
+        const int a = l + kWave * j;
+        if (a < A) {
+            probs[out_row * A + a] = nan_row ? np_softmax_nan<F16>(nan_any) : p[j];
+            beta[out_row * A + a] = nan_row ? np_softmax_nan<F16>(nan_any) : round_as<F16>(q[j] / s2);
+        }
+    }
+}
+
+// The grid of k_policy_glue and k_root_glue is (B, R): root blockIdx.x, agent row blockIdx.y.  Row r
+// takes the A logits (and legal entries) that start r * A past col_off (past the row's start) and is
+// row blockIdx.x * R + r of the [B, R, A] noise and outputs.  R = 1 is one agent at col_off
+// (mz_policy_glue, mz_root_glue and their _wide forms); R = N with col_off = 0 is every agent of a
+// joint search in one launch (mz_policy_glue_joint, mz_root_glue_joint).
+// Two things about the arguments of the glue kernels are there for the launch's cost.  R is an
+// argument: reading gridDim would bring the hidden kernel arguments, 256 bytes more per dispatch, into
+// the launch.  The sum plan comes in A's place (plan_len): the leading 14 dwords of arguments arrive
+// preloaded in SGPRs (the build's kernarg preload), and one argument more, or a struct, which ends
+// that sequence, would leave a fetch of 0.25 us in front of the first use of whatever falls behind.
+template <bool F16, int T>
+__global__ __launch_bounds__(kWave) void k_policy_glue(const void *logits, long long row_stride, long long col_off,
+                                                       unsigned plan, int R, int use_pow, float tau_inv, float *probs,
+                                                       float *beta, const unsigned short *hexp) {
+    const int A = plan_len<T>(plan);
+    __shared__ float lds[kWave * T];
+    policy_glue_row<F16, T>(logits, row_stride, col_off + (long long)blockIdx.y * A, A, plan, use_pow, tau_inv, probs,
+                            beta, hexp, blockIdx.x, (long long)blockIdx.x * R + blockIdx.y, threadIdx.x, lds);
+}
+
+// `x - m` of the root's softmax, m the row's maximum.  When m is a NaN numpy's result is a NaN operand
+// as it stands (x's own where x is one), sign included; the GPU's subtraction negates its second
+// operand first, a NaN's sign with it, so that case is picked by hand.
+__device__ __forceinline__ float np_sub_max(float x, float m) {
+    if (m != m) return (x != x) ? x : m;
+    return x - m;
+}
+
+// Root preprocessing of mcts_sampled.py:64-100 for one (root, agent row) of the grid above (prepare's
+// policy, beta and noise arguments, :102-106), with numpy 2.x's dtype rules (NEP 50):
 //   probs = softmax(logits) in the logits' dtype                                       :64-65
 //   legal (integer array): probs *= legal; probs += legal * 1e-4 (float64 arithmetic, stored in the
 //     logits' dtype); probs /= sum(probs); noises (float32) likewise                     :73-83
 //   beta = probs * (1 - eps) [logits' dtype] + noises * eps [float32] -> float32          :93
 //   beta **= 1 / tau; beta *= legal (float64, stored float32); beta /= sum(beta)          :94-100
-// `legal` holds the agent's row as int32 (the caller checked the integer array's values fit), or is
-// null.  The Dirichlet noise is drawn by the caller (np_random order) and arrives as float32.
-// The body of k_root_glue and of k_root_glue_joint for root t, lane l of its wave: the agent's logits
-// start at element col_off of the root's row, its legal mask at element legal_off of the root's legal
-// row; the noise is read from, and the A results go to, row `out_row` of [rows, A] arrays (lds[kWave]
-// and acc[9] are the workgroup's).
-template <bool F16>
-__device__ __forceinline__ void root_glue_row(const void *logits, long long row_stride, long long col_off, int A,
-                                              const int *legal, long long legal_stride, long long legal_off,
-                                              const float *noise_in, double one_minus_eps, double eps, int use_pow,
-                                              float tau_inv, float *probs, float *beta, float *noise_out,
-                                              const unsigned short *hexp, int t, long long out_row, int l,
-                                              float *lds, float *acc) {
-    const bool on = l < A;
-    const float x = on ? load_elem<F16>(logits, (long long)t * row_stride + col_off + l) : -INFINITY;
-    const bool nan_any = __ballot(on && (x != x)) != 0;
-    const float m = nan_any ? NAN : wave_max(on ? x : -INFINITY);
-    const float d = round_as<F16>(x - m);
-    const float e = np_exp_as<F16>(d, hexp);
-    const float s = round_as<F16>(np_row_sum(e, l, A, lds, acc));
-    float p = round_as<F16>(e / s);
-    float n = on ? noise_in[out_row * A + l] : 0.f;
-    double lg = 0.0;
+// `legal` holds int32 rows (the caller checked the integer array's values fit), or is null.  The
+// Dirichlet noise is drawn by the caller (np_random order) and arrives as float32.  A row that holds
+// a NaN keeps it through np.max and np_sub_max; such rows and rows with an infinite maximum are not
+// pinned against numpy.
+template <bool F16, int T>
+__global__ __launch_bounds__(kWave) void k_root_glue(const void *logits, long long row_stride, long long col_off,
+                                                     unsigned plan, int R, const int *legal, long long legal_stride,
+                                                     const float *noise_in, double one_minus_eps, double eps,
+                                                     int use_pow, float tau_inv, float *probs, float *beta,
+                                                     float *noise_out, const unsigned short *hexp) {
+    const int A = plan_len<T>(plan);
+    __shared__ float lds[kWave * T];
+    const int t = blockIdx.x;
+    const int l = threadIdx.x;
+    const long long agent_off = (long long)blockIdx.y * A, out = ((long long)t * R + blockIdx.y) * A;
+    float x[T], p[T], n[T], b[T];
+    double lg[T];
+#pragma unroll
+    for (int j = 0; j < T; ++j) {
+        const int a = l + kWave * j;
+        x[j] = a < A ? load_elem<F16>(logits, (long long)t * row_stride + col_off + agent_off + a) : -INFINITY;
+        n[j] = a < A ? noise_in[out + a] : 0.f;
+        lg[j] = (legal && a < A) ? (double)legal[(long long)t * legal_stride + agent_off + a] : 0.0;
+    }
+    const float m = np_row_max<T>(x, l, A);
+#pragma unroll
+    for (int j = 0; j < T; ++j) p[j] = np_exp_as<F16>(round_as<F16>(np_sub_max(x[j], m)), hexp);
+    const float s = round_as<F16>(np_row_sum<T>(p, l, A, plan, lds));
+#pragma unroll
+    for (int j = 0; j < T; ++j) p[j] = round_as<F16>(p[j] / s);
     if (legal) {
-        lg = on ? (double)legal[(long long)t * legal_stride + legal_off + l] : 0.0;
-        const double tiny = lg * 1e-4;  // `legal * 1e-4`: a float64 array
-        p = store_d<F16>((double)p * lg);
-        p = store_d<F16>((double)p + tiny);
-        const float sp = round_as<F16>(np_row_sum(p, l, A, lds, acc));
-        p = round_as<F16>(p / sp);
-        n = (float)((double)n * lg);
-        n = (float)((double)n + tiny);
-        const float sn = np_row_sum(n, l, A, lds, acc);
-        n = n / sn;
+#pragma unroll
+        for (int j = 0; j < T; ++j) {
+            const double tiny = lg[j] * 1e-4;  // `legal * 1e-4`: a float64 array
+            p[j] = store_d<F16>((double)p[j] * lg[j]);
+            p[j] = store_d<F16>((double)p[j] + tiny);
+            n[j] = (float)((double)n[j] * lg[j]);
+            n[j] = (float)((double)n[j] + tiny);
+        }
+        const float sp = round_as<F16>(np_row_sum<T>(p, l, A, plan, lds));
+        const float sn = np_row_sum<T>(n, l, A, plan, lds);
+#pragma unroll
+        for (int j = 0; j < T; ++j) {
+            p[j] = round_as<F16>(p[j] / sp);
+            n[j] = n[j] / sn;
+        }
     }
     // probs * (1 - eps): the Python float becomes the array's dtype (NEP 50); noises * eps in float32;
     // the sum of a half and a float32 array is float32
     const float c1 = store_d<F16>(one_minus_eps), c2 = (float)eps;
-    const float a1 = round_as<F16>(p * c1);
-    float b = a1 + n * c2;
-    if (use_pow) b = np_pow_as<false>(b, tau_inv, use_pow);  // a float32 array
-    if (legal) b = (float)((double)b * lg);
-    const float sb = np_row_sum(b, l, A, lds, acc);
-    b = b / sb;
-    if (on) {
-        probs[out_row * A + l] = p;
-        beta[out_row * A + l] = b;
-        noise_out[out_row * A + l] = n;
+#pragma unroll
+    for (int j = 0; j < T; ++j) {
+        const float a1 = round_as<F16>(p[j] * c1);
+        b[j] = a1 + n[j] * c2;
+        if (use_pow) b[j] = np_pow_as<false>(b[j], tau_inv, use_pow);  // a float32 array
+        if (legal) b[j] = (float)((double)b[j] * lg[j]);
     }
-}
-
-template <bool F16>
-__global__ __launch_bounds__(kWave) void k_root_glue(const void *logits, long long row_stride, long long col_off,
-                                                     int A, const int *legal, long long legal_stride,
-                                                     const float *noise_in, double one_minus_eps, double eps,
-                                                     int use_pow, float tau_inv, float *probs, float *beta,
-                                                     float *noise_out, const unsigned short *hexp) {
-    __shared__ float lds[kWave];
-    __shared__ float acc[9];
-    root_glue_row<F16>(logits, row_stride, col_off, A, legal, legal_stride, 0, noise_in, one_minus_eps, eps, use_pow,
-                       tau_inv, probs, beta, noise_out, hexp, blockIdx.x, blockIdx.x, threadIdx.x, lds, acc);
-}
-
-// mz_root_glue_joint: k_root_glue for every agent of a joint search in one launch, one wave per
-// (root, agent), workgroup t * N + k.  Agent k's logits and legal mask start at element k * A of root
-// t's rows; its noise and its results are row t * N + k of [B, N, A] arrays.
-template <bool F16>
-__global__ __launch_bounds__(kWave) void k_root_glue_joint(const void *logits, long long row_stride, int N, int A,
-                                                           const int *legal, long long legal_stride,
-                                                           const float *noise_in, double one_minus_eps, double eps,
-                                                           int use_pow, float tau_inv, float *probs, float *beta,
-                                                           float *noise_out, const unsigned short *hexp) {
-    __shared__ float lds[kWave];
-    __shared__ float acc[9];
-    const int t = (int)(blockIdx.x / (unsigned)N), k = (int)(blockIdx.x % (unsigned)N);
-    root_glue_row<F16>(logits, row_stride, (long long)k * A, A, legal, legal_stride, (long long)k * A, noise_in,
-                       one_minus_eps, eps, use_pow, tau_inv, probs, beta, noise_out, hexp, t, (long long)blockIdx.x,
-                       threadIdx.x, lds, acc);
+    const float sb = np_row_sum<T>(b, l, A, plan, lds);
+#pragma unroll
+    for (int j = 0; j < T; ++j) {
+        const int a = l + kWave * j;
+        if (a < A) {
+            probs[out + a] = p[j];
+            beta[out + a] = b[j] / sb;
+            noise_out[out + a] = n[j];
+        }
+    }
 }
 
 // mcts_sampled.py:116-147 for root blockIdx.x: previous agents from `factor`, the current agent
 // from the selection, the following agents by numpy argmax of the leaf policy logits.
-template <bool F16>
+template <bool F16, int T>
 __global__ __launch_bounds__(kWave) void k_joint_action(const void *pred, int N, int A, int cur, const int *factor,
                                                         int fcols, const int *actions, long long *joint) {
     const int t = blockIdx.x;
@@ -361,7 +473,7 @@ __global__ __launch_bounds__(kWave) void k_joint_action(const void *pred, int N,
     if (l < N && l <= cur) joint[(long long)t * N + l] = (l < cur) ? (long long)factor[(long long)t * fcols + l]
                                                                     : (long long)actions[t];
     for (int k = cur + 1; k < N; ++k) {
-        const int idx = np_argmax_row<F16>(pred, ((long long)t * N + k) * A, A, l);
+        const int idx = np_argmax_row<F16, T>(pred, ((long long)t * N + k) * A, A, l);
         if (l == 0) joint[(long long)t * N + k] = idx;
     }
 }
@@ -370,24 +482,24 @@ __global__ __launch_bounds__(kWave) void k_joint_action(const void *pred, int N,
 // current agent (absent when the caller wants the later agents only: then `glue` is 0 and every role
 // is an argmax); role j >= 1 is np.argmax of agent cur + j's logits into later[t, cur + j].  The role
 // is the workgroup's, so the ballots and wave_max of either body stay in wave-uniform control flow.
-constexpr int kMaxLaterAgents = 65535;  // a role per agent in grid.y
-template <bool F16>
-__global__ __launch_bounds__(kWave) void k_policy_glue_later(const void *logits, long long row_stride, int N, int A,
+constexpr int kMaxGridRows = 65535;  // grid.y: a role per agent here, an agent per row in the joint glue
+template <bool F16, int T>
+__global__ __launch_bounds__(kWave) void k_policy_glue_later(const void *logits, long long row_stride, int N, unsigned plan,
                                                              int cur, int glue, int use_pow, float tau_inv,
                                                              float *probs, float *beta, int *later,
                                                              const unsigned short *hexp) {
-    __shared__ float lds[kWave];
-    __shared__ float acc[9];
+    const int A = plan_len<T>(plan);
+    __shared__ float lds[kWave * T];
     const int t = blockIdx.x;
     const int l = threadIdx.x;
     const int j = (int)blockIdx.y + 1 - glue;
     if (j == 0) {
-        policy_glue_row<F16>(logits, row_stride, (long long)cur * A, A, use_pow, tau_inv, probs, beta, hexp, t, t, l,
-                             lds, acc);
+        policy_glue_row<F16, T>(logits, row_stride, (long long)cur * A, A, plan, use_pow, tau_inv, probs, beta, hexp, t,
+                                t, l, lds);
         return;
     }
     const int k = cur + j;
-    const int idx = np_argmax_row<F16>(logits, (long long)t * row_stride + (long long)k * A, A, l);
+    const int idx = np_argmax_row<F16, T>(logits, (long long)t * row_stride + (long long)k * A, A, l);
     if (l == 0) later[(long long)t * N + k] = idx;
 }
 
@@ -412,283 +524,6 @@ __global__ __launch_bounds__(kCachedLanes) void k_joint_action_cached(const int 
         v = pool[((long long)s * B + i) * N + k];
     }
     joint[e] = v;
-}
-
-// ------------------------------------------------------------------------------------------------
-// Action spaces past one wave (64 < A <= 255): still one wave per root; lane l holds the actions
-// l + 64 j, j < T = ceil(A / 64), in registers (T is a template parameter: the tile loops unroll).
-// The elementwise arithmetic is that of the kernels above; only the row reductions differ.
-//
-// np.sum(axis=-1) of a row of n > 128 elements is no longer one base case: numpy's pairwise sum
-// splits at n2 = n / 2, n2 -= n2 % 8 and adds pairwise(a, n2) + pairwise(a + n2, n - n2),
-// recursively.  For n <= 255 the first half (<= 120) is always a base case and the second (<= 135)
-// splits at most once more, so a row is at most three base-case blocks, each starting at a multiple
-// of 8, joined from the right: s0, s0 + s1 or s0 + (s1 + s2).  The launcher walks the recursion
-// once (sum_plan) and hands the kernel the blocks.
-constexpr int kWideMax = 255;       // the handle's own limit (a node packs its action in 8 bits)
-constexpr int kWideRow = 256;       // LDS row: every index below is < A <= 255
-constexpr int kPairwiseBlock = 128; // numpy's PW_BLOCKSIZE
-constexpr int kMaxBlocks = 3;
-
-struct SumPlan {
-    unsigned start;  // byte b: first element of block b
-    unsigned len;    // byte b: its length (1..128), 0: no such block
-};
-
-// the base-case blocks of numpy's pairwise sum over n elements, in row order; returns their count,
-// or -1 when the join is not the right-nested one the kernels apply (never for n <= 255)
-int sum_plan_blocks(int start, int n, int *starts, int *lens, int k, int cap) {
-    if (n <= kPairwiseBlock) {
-        if (k >= cap) return -1;
-        starts[k] = start;
-        lens[k] = n;
-        return k + 1;
-    }
-    int n2 = n / 2;
-    n2 -= n2 % 8;
-    if (n2 > kPairwiseBlock) return -1;  // a left half that splits: (s0 + s1) + ..., not restated
-    k = sum_plan_blocks(start, n2, starts, lens, k, cap);
-    if (k < 0) return k;
-    return sum_plan_blocks(start + n2, n - n2, starts, lens, k, cap);
-}
-
-bool sum_plan(int n, SumPlan *plan) {
-    int starts[kMaxBlocks] = {0, 0, 0}, lens[kMaxBlocks] = {0, 0, 0};
-    if (n < 1 || n > kWideMax || sum_plan_blocks(0, n, starts, lens, 0, kMaxBlocks) < 1) return false;
-    plan->start = (unsigned)starts[0] | (unsigned)starts[1] << 8 | (unsigned)starts[2] << 16;
-    plan->len = (unsigned)lens[0] | (unsigned)lens[1] << 8 | (unsigned)lens[2] << 16;
-    return true;
-}
-
-// np.sum over the row whose element l + 64 j is v[j]; result in every lane.  Lanes 8 b + i run
-// accumulator i of block b; the 8 accumulators combine as a butterfly, which is numpy's
-// ((r0+r1)+(r2+r3))+((r4+r5)+(r6+r7)) in every lane of the group (float addition commutes); lane 8 b
-// adds the block's n % 8 tail; the block sums join from the right.
-template <int T>
-__device__ float np_row_sum_wide(const float (&v)[T], int l, int A, SumPlan plan, float *lds) {
-#pragma unroll
-    for (int j = 0; j < T; ++j)
-        if (l + kWave * j < A) lds[l + kWave * j] = v[j];
-    __syncthreads();
-    const int blk = l >> 3, i = l & 7;
-    const int start = blk < kMaxBlocks ? (int)(plan.start >> (8 * blk) & 0xffu) : 0;
-    const int len = blk < kMaxBlocks ? (int)(plan.len >> (8 * blk) & 0xffu) : 0;
-    // (a block of a row of more than 64 elements holds at least 64: numpy's sequential sum of fewer
-    // than 8 elements never applies here; lanes past the last block idle with len = 0)
-    const int n8 = len - len % 8;
-    float r = 0.f;
-    if (len) {
-        r = lds[start + i];
-        for (int k = 8; k < n8; k += 8) r += lds[start + k + i];
-    }
-    r += __shfl_xor(r, 1, kWave);
-    r += __shfl_xor(r, 2, kWave);
-    r += __shfl_xor(r, 4, kWave);
-    if (i == 0)
-        for (int k = n8; k < len; ++k) r += lds[start + k];
-    const float s0 = __shfl(r, 0, kWave), s1 = __shfl(r, 8, kWave), s2 = __shfl(r, 16, kWave);
-    __syncthreads();  // (the row is read: the next sum may overwrite it)
-    if (plan.len >> 16) return s0 + (s1 + s2);
-    if (plan.len >> 8) return s0 + s1;
-    return s0;
-}
-
-// np.max(axis=-1) of the row: a NaN anywhere makes it that NaN (one ballot per tile; the first in
-// action order where the row holds several)
-template <int T>
-__device__ __forceinline__ float np_row_max_wide(const float (&x)[T], int l, int A) {
-    bool nan_any = false;
-    float m = -INFINITY, nan_v = 0.f;
-#pragma unroll
-    for (int j = 0; j < T; ++j) {
-        const bool on = l + kWave * j < A;
-        const unsigned long long nan_mask = __ballot(on && (x[j] != x[j]));
-        if (!nan_any && nan_mask) {  // (wave-uniform)
-            nan_any = true;
-            nan_v = __shfl(x[j], __ffsll((long long)nan_mask) - 1, kWave);
-        }
-        m = fmaxf(m, on ? x[j] : -INFINITY);
-    }
-    return nan_any ? nan_v : wave_max(m);
-}
-
-// `x - m` of the softmax, m the row's maximum.  When m is a NaN numpy's result is a NaN operand as it
-// stands (x's own where x is one), sign included; the GPU's subtraction negates its second operand
-// first, a NaN's sign with it, so that case is picked by hand.
-__device__ __forceinline__ float np_sub_max(float x, float m) {
-    if (m != m) return (x != x) ? x : m;
-    return x - m;
-}
-
-// policy_glue_row for 64 < A <= 255: the body of k_policy_glue_wide and of role 0 of
-// k_policy_glue_later_wide (lds[kWideRow] is the workgroup's)
-template <bool F16, int T>
-__device__ __forceinline__ void policy_glue_row_wide(const void *logits, long long row_stride, long long col_off,
-                                                     int A, SumPlan plan, int use_pow, float tau_inv, float *probs,
-                                                     float *beta, const unsigned short *hexp, int t, int l,
-                                                     float *lds) {
-    float x[T], e[T], p[T], q[T];
-#pragma unroll
-    for (int j = 0; j < T; ++j) {
-        const int a = l + kWave * j;
-        x[j] = a < A ? load_elem<F16>(logits, (long long)t * row_stride + col_off + a) : -INFINITY;
-    }
-    const float m = np_row_max_wide<T>(x, l, A);
-#pragma unroll
-    for (int j = 0; j < T; ++j) e[j] = np_exp_as<F16>(round_as<F16>(np_sub_max(x[j], m)), hexp);
-    const float s = round_as<F16>(np_row_sum_wide<T>(e, l, A, plan, lds));
-#pragma unroll
-    for (int j = 0; j < T; ++j) {
-        p[j] = round_as<F16>(e[j] / s);
-        q[j] = use_pow ? np_pow_as<F16>(p[j], tau_inv, use_pow) : p[j];
-    }
-    const float s2 = round_as<F16>(np_row_sum_wide<T>(q, l, A, plan, lds));
-#pragma unroll
-    for (int j = 0; j < T; ++j) {
-        const int a = l + kWave * j;
-        if (a < A) {
-            probs[(long long)t * A + a] = p[j];
-            beta[(long long)t * A + a] = round_as<F16>(q[j] / s2);
-        }
-    }
-}
-
-// k_policy_glue for 64 < A <= 255
-template <bool F16, int T>
-__global__ __launch_bounds__(kWave) void k_policy_glue_wide(const void *logits, long long row_stride,
-                                                            long long col_off, int A, SumPlan plan, int use_pow,
-                                                            float tau_inv, float *probs, float *beta,
-                                                            const unsigned short *hexp) {
-    __shared__ float lds[kWideRow];
-    policy_glue_row_wide<F16, T>(logits, row_stride, col_off, A, plan, use_pow, tau_inv, probs, beta, hexp,
-                                 blockIdx.x, threadIdx.x, lds);
-}
-
-// k_root_glue for 64 < A <= 255
-template <bool F16, int T>
-__global__ __launch_bounds__(kWave) void k_root_glue_wide(const void *logits, long long row_stride, long long col_off,
-                                                          int A, SumPlan plan, const int *legal,
-                                                          long long legal_stride, const float *noise_in,
-                                                          double one_minus_eps, double eps, int use_pow,
-                                                          float tau_inv, float *probs, float *beta,
-                                                          float *noise_out, const unsigned short *hexp) {
-    __shared__ float lds[kWideRow];
-    const int t = blockIdx.x;
-    const int l = threadIdx.x;
-    float x[T], p[T], n[T], b[T];
-    double lg[T];
-#pragma unroll
-    for (int j = 0; j < T; ++j) {
-        const int a = l + kWave * j;
-        x[j] = a < A ? load_elem<F16>(logits, (long long)t * row_stride + col_off + a) : -INFINITY;
-        n[j] = a < A ? noise_in[(long long)t * A + a] : 0.f;
-        lg[j] = (legal && a < A) ? (double)legal[(long long)t * legal_stride + a] : 0.0;
-    }
-    const float m = np_row_max_wide<T>(x, l, A);
-#pragma unroll
-    for (int j = 0; j < T; ++j) p[j] = np_exp_as<F16>(round_as<F16>(np_sub_max(x[j], m)), hexp);
-    const float s = round_as<F16>(np_row_sum_wide<T>(p, l, A, plan, lds));
-#pragma unroll
-    for (int j = 0; j < T; ++j) p[j] = round_as<F16>(p[j] / s);
-    if (legal) {
-#pragma unroll
-        for (int j = 0; j < T; ++j) {
-            const double tiny = lg[j] * 1e-4;  // `legal * 1e-4`: a float64 array
-            p[j] = store_d<F16>((double)p[j] * lg[j]);
-            p[j] = store_d<F16>((double)p[j] + tiny);
-            n[j] = (float)((double)n[j] * lg[j]);
-            n[j] = (float)((double)n[j] + tiny);
-        }
-        const float sp = round_as<F16>(np_row_sum_wide<T>(p, l, A, plan, lds));
-        const float sn = np_row_sum_wide<T>(n, l, A, plan, lds);
-#pragma unroll
-        for (int j = 0; j < T; ++j) {
-            p[j] = round_as<F16>(p[j] / sp);
-            n[j] = n[j] / sn;
-        }
-    }
-    const float c1 = store_d<F16>(one_minus_eps), c2 = (float)eps;
-#pragma unroll
-    for (int j = 0; j < T; ++j) {
-        const float a1 = round_as<F16>(p[j] * c1);
-        b[j] = a1 + n[j] * c2;
-        if (use_pow) b[j] = np_pow_as<false>(b[j], tau_inv, use_pow);  // a float32 array
-        if (legal) b[j] = (float)((double)b[j] * lg[j]);
-    }
-    const float sb = np_row_sum_wide<T>(b, l, A, plan, lds);
-#pragma unroll
-    for (int j = 0; j < T; ++j) {
-        const int a = l + kWave * j;
-        if (a < A) {
-            probs[(long long)t * A + a] = p[j];
-            beta[(long long)t * A + a] = b[j] / sb;
-            noise_out[(long long)t * A + a] = n[j];
-        }
-    }
-}
-
-// np_argmax_row for 64 < A <= 255 (k_joint_action_wide, k_policy_glue_later_wide).  np.argmax: the
-// smallest action holding a NaN if there is one, else the smallest action equal to the maximum.
-// Action l + 64 j orders by tile first, so the tiles are scanned in order and the first set ballot bit
-// taken inside a tile.
-template <bool F16, int T>
-__device__ __forceinline__ int np_argmax_row_wide(const void *p, long long row, int A, int l) {
-    float v[T];
-    float m = -INFINITY;
-    int idx = -1;
-#pragma unroll
-    for (int j = 0; j < T; ++j) {
-        const int a = l + kWave * j;
-        const bool on = a < A;
-        v[j] = on ? load_elem<F16>(p, row + a) : -INFINITY;
-        m = fmaxf(m, v[j]);
-        const unsigned long long nan_mask = __ballot(on && (v[j] != v[j]));
-        if (idx < 0 && nan_mask) idx = kWave * j + __ffsll((long long)nan_mask) - 1;
-    }
-    if (idx < 0) {  // (wave-uniform)
-        m = wave_max(m);
-#pragma unroll
-        for (int j = 0; j < T; ++j) {
-            const unsigned long long hit = __ballot(l + kWave * j < A && v[j] == m);
-            if (idx < 0 && hit) idx = kWave * j + __ffsll((long long)hit) - 1;
-        }
-    }
-    return idx;
-}
-
-template <bool F16, int T>
-__global__ __launch_bounds__(kWave) void k_joint_action_wide(const void *pred, int N, int A, int cur,
-                                                             const int *factor, int fcols, const int *actions,
-                                                             long long *joint) {
-    const int t = blockIdx.x;
-    const int l = threadIdx.x;
-    if (l < N && l <= cur) joint[(long long)t * N + l] = (l < cur) ? (long long)factor[(long long)t * fcols + l]
-                                                                    : (long long)actions[t];
-    for (int k = cur + 1; k < N; ++k) {
-        const int idx = np_argmax_row_wide<F16, T>(pred, ((long long)t * N + k) * A, A, l);
-        if (l == 0) joint[(long long)t * N + k] = idx;
-    }
-}
-
-// k_policy_glue_later for 64 < A <= 255
-template <bool F16, int T>
-__global__ __launch_bounds__(kWave) void k_policy_glue_later_wide(const void *logits, long long row_stride, int N,
-                                                                  int A, int cur, int glue, SumPlan plan,
-                                                                  int use_pow, float tau_inv, float *probs,
-                                                                  float *beta, int *later,
-                                                                  const unsigned short *hexp) {
-    __shared__ float lds[kWideRow];
-    const int t = blockIdx.x;
-    const int l = threadIdx.x;
-    const int j = (int)blockIdx.y + 1 - glue;
-    if (j == 0) {
-        policy_glue_row_wide<F16, T>(logits, row_stride, (long long)cur * A, A, plan, use_pow, tau_inv, probs, beta,
-                                     hexp, t, l, lds);
-        return;
-    }
-    const int k = cur + j;
-    const int idx = np_argmax_row_wide<F16, T>(logits, (long long)t * row_stride + (long long)k * A, A, l);
-    if (l == 0) later[(long long)t * N + k] = idx;
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -962,6 +797,105 @@ const unsigned short *half_exp_table() {
     return g_half_exp[dev];
 }
 
+// ------------------------------------------------------------------------------------------------
+// What the glue launchers share.  `fn` names the entry point in the messages.  Every entry point
+// checks its arguments in an order of its own, so the shared steps are separate calls.
+int glue_fail(int code, const char *fn, const char *what) {
+    return mz_internal_fail(code, (std::string(fn) + ": " + what).c_str());
+}
+
+struct Glue {
+    const char *fn;
+    mz_batch *b;
+    int B = 0, A = 0;
+    hipStream_t stream = nullptr;
+    unsigned plan = 0u;  // sum_plan(A)
+    int use_pow = 0;     // `** (1 / sampled_tau)`: pow_mode and the exponent as numpy casts it
+    float tau_inv = 1.f;
+    const unsigned short *hexp = nullptr;
+};
+
+// the handle's device current, its B, A and stream
+int glue_handle(Glue *g, const char *fn, mz_batch *b) {
+    g->fn = fn;
+    g->b = b;
+    return mz_internal_launch_info(b, &g->B, &g->A, &g->stream);
+}
+
+// glue_handle for an entry point that reads rows of A actions: A within its bound, one lane per action,
+// or with `wide` every A the handle has (the kernels are the same, include/mzdriver.h)
+int glue_begin(Glue *g, const char *fn, mz_batch *b, bool wide) {
+    if (int rc = glue_handle(g, fn, b)) return rc;
+    if (!wide && g->A > kWave) return glue_fail(MZ_ERR_UNSUPPORTED, fn, "action_space_size > 64");
+    if (g->A > kWideMax) return glue_fail(MZ_ERR_UNSUPPORTED, fn, "action_space_size > 255");
+    g->plan = sum_plan(g->A);
+    return MZ_OK;
+}
+
+int glue_dtype(const Glue &g, int dtype) {
+    if (dtype != MZ_DT_F32 && dtype != MZ_DT_F16) return glue_fail(MZ_ERR_ARG, g.fn, "bad dtype");
+    return MZ_OK;
+}
+
+// Python's `1 / sampled_tau`, cast to the dtype of the array it raises (NEP 50): the logits' for the
+// policy glue (`half`: float16), float32 for the root's beta; and the softmax's half-exp table
+int glue_tau(Glue *g, double sampled_tau, bool half) {
+    if (!(sampled_tau > 0.0)) return glue_fail(MZ_ERR_ARG, g->fn, "sampled_tau must be > 0");
+    const double inv = 1.0 / sampled_tau;
+    g->tau_inv = half ? (float)(_Float16)inv : (float)inv;
+    g->use_pow = pow_mode(inv);
+    g->hexp = half_exp_table();
+    return MZ_OK;
+}
+
+// (dtype, A) -> <F16, T = ceil(A / 64)>: launch(std::bool_constant<F16>, std::integral_constant<int, T>)
+template <class Launch>
+void glue_dispatch(int dtype, int A, Launch launch) {
+    auto tiles = [&](auto f16) {
+        switch ((A + kWave - 1) / kWave) {
+            case 1: launch(f16, std::integral_constant<int, 1>{}); break;
+            case 2: launch(f16, std::integral_constant<int, 2>{}); break;
+            case 3: launch(f16, std::integral_constant<int, 3>{}); break;
+            default: launch(f16, std::integral_constant<int, 4>{}); break;
+        }
+    };
+    if (dtype == MZ_DT_F16)
+        tiles(std::true_type{});
+    else
+        tiles(std::false_type{});
+}
+
+int glue_end(const Glue &g) {
+    mz_internal_enqueued(g.b);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return mz_internal_fail(MZ_ERR_DEVICE, hipGetErrorString(e));
+    return MZ_OK;
+}
+
+// k_policy_glue / k_root_glue on a grid of (B, rows)
+int launch_policy_glue(const Glue &g, int dtype, int rows, const void *logits, int64_t row_stride,
+                       int64_t col_offset, float *probs_out, float *beta_out) {
+    glue_dispatch(dtype, g.A, [&](auto f16, auto tiles) {
+        hipLaunchKernelGGL((k_policy_glue<decltype(f16)::value, decltype(tiles)::value>), dim3(g.B, rows),
+                           dim3(kWave), 0, g.stream, logits, (long long)row_stride, (long long)col_offset, g.plan, rows,
+                           g.use_pow, g.tau_inv, probs_out, beta_out, g.hexp);
+    });
+    return glue_end(g);
+}
+
+int launch_root_glue(const Glue &g, int dtype, int rows, const void *logits, int64_t row_stride, int64_t col_offset,
+                     const int32_t *legal, int64_t legal_stride, const float *noises, double noise_eps,
+                     float *probs_out, float *beta_out, float *noises_out) {
+    const double ome = 1.0 - noise_eps;  // (Python float arithmetic)
+    glue_dispatch(dtype, g.A, [&](auto f16, auto tiles) {
+        hipLaunchKernelGGL((k_root_glue<decltype(f16)::value, decltype(tiles)::value>), dim3(g.B, rows), dim3(kWave),
+                           0, g.stream, logits, (long long)row_stride, (long long)col_offset, g.plan, rows,
+                           (const int *)legal, (long long)legal_stride, noises, ome, noise_eps, g.use_pow,
+                           g.tau_inv, probs_out, beta_out, noises_out, g.hexp);
+    });
+    return glue_end(g);
+}
+
 }  // namespace
 
 extern "C" {
@@ -984,126 +918,39 @@ int mz_set_half_exp_table(const uint16_t *table) {
     return MZ_OK;
 }
 
-// The launchers.  `fn` names the entry point in the messages; `wide` (the _wide entry points) takes
-// any A the handle has and launches the kernels above for A > 64, the one-lane-per-action kernels
-// otherwise, so that A <= 64 computes the same through either entry point.
-static int glue_fail(int code, const char *fn, const char *what) {
-    return mz_internal_fail(code, (std::string(fn) + ": " + what).c_str());
-}
-
-// T = ceil(A / 64) in {2, 3, 4} as a template argument of a wide kernel
-#define MZ_WIDE_TILES(A, LAUNCH)          \
-    do {                                  \
-        switch (((A) + kWave - 1) / kWave) { \
-            case 2: LAUNCH(2); break;     \
-            case 3: LAUNCH(3); break;     \
-            default: LAUNCH(4); break;    \
-        }                                 \
-    } while (0)
-
+// mz_policy_glue, mz_root_glue, mz_joint_action and their _wide forms (`wide`: any A the handle has)
 static int policy_glue(const char *fn, bool wide, mz_batch *b, const void *logits, int dtype, int64_t row_stride,
                        int64_t col_offset, double sampled_tau, float *probs_out, float *beta_out) {
-    int B = 0, A = 0;
-    hipStream_t stream = nullptr;
-    int rc = mz_internal_launch_info(b, &B, &A, &stream);
-    if (rc) return rc;
-    if (!wide && A > kWave)  // (one lane per action; the tree itself takes up to 255 actions)
-        return glue_fail(MZ_ERR_UNSUPPORTED, fn, "action_space_size > 64");
-    SumPlan plan{};
-    if (A > kWave && !sum_plan(A, &plan)) return glue_fail(MZ_ERR_UNSUPPORTED, fn, "action_space_size > 255");
+    Glue g;
+    if (int rc = glue_begin(&g, fn, b, wide)) return rc;
     if (!logits || !probs_out || !beta_out) return glue_fail(MZ_ERR_ARG, fn, "null buffer");
-    if (dtype != MZ_DT_F32 && dtype != MZ_DT_F16) return glue_fail(MZ_ERR_ARG, fn, "bad dtype");
-    if (row_stride < A || col_offset < 0 || col_offset + A > row_stride)
+    if (int rc = glue_dtype(g, dtype)) return rc;
+    if (row_stride < g.A || col_offset < 0 || col_offset + g.A > row_stride)
         return glue_fail(MZ_ERR_ARG, fn, "logits row does not hold the agent's actions");
-    if (!(sampled_tau > 0.0)) return glue_fail(MZ_ERR_ARG, fn, "sampled_tau must be > 0");
-    const double inv = 1.0 / sampled_tau;  // Python's `1 / sampled_tau`, cast to the array's dtype
-    const float tau_inv = (dtype == MZ_DT_F16) ? (float)(_Float16)inv : (float)inv;
-    const int use_pow = pow_mode(inv);
-    const unsigned short *hexp = half_exp_table();
-    if (A > kWave) {
-#define MZ_LAUNCH(T)                                                                                              \
-    if (dtype == MZ_DT_F16)                                                                                       \
-        hipLaunchKernelGGL((k_policy_glue_wide<true, T>), dim3(B), dim3(kWave), 0, stream, logits,                \
-                           (long long)row_stride, (long long)col_offset, A, plan, use_pow, tau_inv, probs_out,    \
-                           beta_out, hexp);                                                                       \
-    else                                                                                                          \
-        hipLaunchKernelGGL((k_policy_glue_wide<false, T>), dim3(B), dim3(kWave), 0, stream, logits,               \
-                           (long long)row_stride, (long long)col_offset, A, plan, use_pow, tau_inv, probs_out,    \
-                           beta_out, hexp)
-        MZ_WIDE_TILES(A, MZ_LAUNCH);
-#undef MZ_LAUNCH
-    } else if (dtype == MZ_DT_F16)
-        hipLaunchKernelGGL(k_policy_glue<true>, dim3(B), dim3(kWave), 0, stream, logits, (long long)row_stride,
-                           (long long)col_offset, A, use_pow, tau_inv, probs_out, beta_out, hexp);
-    else
-        hipLaunchKernelGGL(k_policy_glue<false>, dim3(B), dim3(kWave), 0, stream, logits, (long long)row_stride,
-                           (long long)col_offset, A, use_pow, tau_inv, probs_out, beta_out, hexp);
-    mz_internal_enqueued(b);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return mz_internal_fail(MZ_ERR_DEVICE, hipGetErrorString(e));
-    return MZ_OK;
+    if (int rc = glue_tau(&g, sampled_tau, dtype == MZ_DT_F16)) return rc;
+    return launch_policy_glue(g, dtype, 1, logits, row_stride, col_offset, probs_out, beta_out);
 }
 
 static int root_glue(const char *fn, bool wide, mz_batch *b, const void *logits, int dtype, int64_t row_stride,
                      int64_t col_offset, const int32_t *legal, int64_t legal_stride, const float *noises,
                      double noise_eps, double sampled_tau, float *probs_out, float *beta_out, float *noises_out) {
-    int B = 0, A = 0;
-    hipStream_t stream = nullptr;
-    int rc = mz_internal_launch_info(b, &B, &A, &stream);
-    if (rc) return rc;
-    if (!wide && A > kWave)  // (one lane per action; the tree itself takes up to 255 actions)
-        return glue_fail(MZ_ERR_UNSUPPORTED, fn, "action_space_size > 64");
-    SumPlan plan{};
-    if (A > kWave && !sum_plan(A, &plan)) return glue_fail(MZ_ERR_UNSUPPORTED, fn, "action_space_size > 255");
+    Glue g;
+    if (int rc = glue_begin(&g, fn, b, wide)) return rc;
     if (!logits || !noises || !probs_out || !beta_out || !noises_out) return glue_fail(MZ_ERR_ARG, fn, "null buffer");
-    if (dtype != MZ_DT_F32 && dtype != MZ_DT_F16) return glue_fail(MZ_ERR_ARG, fn, "bad dtype");
-    if (row_stride < A || col_offset < 0 || col_offset + A > row_stride)
+    if (int rc = glue_dtype(g, dtype)) return rc;
+    if (row_stride < g.A || col_offset < 0 || col_offset + g.A > row_stride)
         return glue_fail(MZ_ERR_ARG, fn, "logits row does not hold the agent's actions");
-    if (legal && legal_stride < A) return glue_fail(MZ_ERR_ARG, fn, "legal rows hold fewer than A");
-    if (!(sampled_tau > 0.0)) return glue_fail(MZ_ERR_ARG, fn, "sampled_tau must be > 0");
-    const double inv = 1.0 / sampled_tau;  // beta is a float32 array here (:93)
-    const float tau_inv = (float)inv;
-    const int use_pow = pow_mode(inv);
-    const double ome = 1.0 - noise_eps;  // (Python float arithmetic)
-    const unsigned short *hexp = half_exp_table();
-    if (A > kWave) {
-#define MZ_LAUNCH(T)                                                                                              \
-    if (dtype == MZ_DT_F16)                                                                                       \
-        hipLaunchKernelGGL((k_root_glue_wide<true, T>), dim3(B), dim3(kWave), 0, stream, logits,                  \
-                           (long long)row_stride, (long long)col_offset, A, plan, (const int *)legal,             \
-                           (long long)legal_stride, noises, ome, noise_eps, use_pow, tau_inv, probs_out,          \
-                           beta_out, noises_out, hexp);                                                           \
-    else                                                                                                          \
-        hipLaunchKernelGGL((k_root_glue_wide<false, T>), dim3(B), dim3(kWave), 0, stream, logits,                 \
-                           (long long)row_stride, (long long)col_offset, A, plan, (const int *)legal,             \
-                           (long long)legal_stride, noises, ome, noise_eps, use_pow, tau_inv, probs_out,          \
-                           beta_out, noises_out, hexp)
-        MZ_WIDE_TILES(A, MZ_LAUNCH);
-#undef MZ_LAUNCH
-    } else if (dtype == MZ_DT_F16)
-        hipLaunchKernelGGL(k_root_glue<true>, dim3(B), dim3(kWave), 0, stream, logits, (long long)row_stride,
-                           (long long)col_offset, A, (const int *)legal, (long long)legal_stride, noises, ome,
-                           noise_eps, use_pow, tau_inv, probs_out, beta_out, noises_out, hexp);
-    else
-        hipLaunchKernelGGL(k_root_glue<false>, dim3(B), dim3(kWave), 0, stream, logits, (long long)row_stride,
-                           (long long)col_offset, A, (const int *)legal, (long long)legal_stride, noises, ome,
-                           noise_eps, use_pow, tau_inv, probs_out, beta_out, noises_out, hexp);
-    mz_internal_enqueued(b);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return mz_internal_fail(MZ_ERR_DEVICE, hipGetErrorString(e));
-    return MZ_OK;
+    if (legal && legal_stride < g.A) return glue_fail(MZ_ERR_ARG, fn, "legal rows hold fewer than A");
+    if (int rc = glue_tau(&g, sampled_tau, false)) return rc;  // beta is a float32 array here (:93)
+    return launch_root_glue(g, dtype, 1, logits, row_stride, col_offset, legal, legal_stride, noises, noise_eps,
+                            probs_out, beta_out, noises_out);
 }
 
 static int joint_action(const char *fn, bool wide, mz_batch *b, const void *pred_logits, int dtype, int num_agents,
                         int current_agent, const int32_t *factor, int factor_cols, const int32_t *actions,
                         int64_t *joint_out) {
-    int B = 0, A = 0;
-    hipStream_t stream = nullptr;
-    int rc = mz_internal_launch_info(b, &B, &A, &stream);
-    if (rc) return rc;
-    if (!wide && A > kWave)  // (one lane per action; the tree itself takes up to 255 actions)
-        return glue_fail(MZ_ERR_UNSUPPORTED, fn, "action_space_size > 64");
-    if (A > kWideMax) return glue_fail(MZ_ERR_UNSUPPORTED, fn, "action_space_size > 255");
+    Glue g;
+    if (int rc = glue_begin(&g, fn, b, wide)) return rc;
     if (num_agents < 1 || num_agents > kWave || current_agent < 0 || current_agent >= num_agents)
         return glue_fail(MZ_ERR_ARG, fn, "bad agent index / count");
     if (!actions || !joint_out) return glue_fail(MZ_ERR_ARG, fn, "null buffer");
@@ -1111,185 +958,94 @@ static int joint_action(const char *fn, bool wide, mz_batch *b, const void *pred
         return glue_fail(MZ_ERR_ARG, fn, "factor must hold the previous agents' actions");
     if (current_agent + 1 < num_agents && !pred_logits)
         return glue_fail(MZ_ERR_ARG, fn, "leaf policy logits required for later agents");
-    if (dtype != MZ_DT_F32 && dtype != MZ_DT_F16) return glue_fail(MZ_ERR_ARG, fn, "bad dtype");
-    if (A > kWave) {
-#define MZ_LAUNCH(T)                                                                                              \
-    if (dtype == MZ_DT_F16)                                                                                       \
-        hipLaunchKernelGGL((k_joint_action_wide<true, T>), dim3(B), dim3(kWave), 0, stream, pred_logits,          \
-                           num_agents, A, current_agent, (const int *)factor, factor_cols,                        \
-                           (const int *)actions, (long long *)joint_out);                                         \
-    else                                                                                                          \
-        hipLaunchKernelGGL((k_joint_action_wide<false, T>), dim3(B), dim3(kWave), 0, stream, pred_logits,         \
-                           num_agents, A, current_agent, (const int *)factor, factor_cols,                        \
-                           (const int *)actions, (long long *)joint_out)
-        MZ_WIDE_TILES(A, MZ_LAUNCH);
-#undef MZ_LAUNCH
-    } else if (dtype == MZ_DT_F16)
-        hipLaunchKernelGGL(k_joint_action<true>, dim3(B), dim3(kWave), 0, stream, pred_logits, num_agents, A,
-                           current_agent, (const int *)factor, factor_cols, (const int *)actions,
-                           (long long *)joint_out);
-    else
-        hipLaunchKernelGGL(k_joint_action<false>, dim3(B), dim3(kWave), 0, stream, pred_logits, num_agents, A,
-                           current_agent, (const int *)factor, factor_cols, (const int *)actions,
-                           (long long *)joint_out);
-    mz_internal_enqueued(b);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return mz_internal_fail(MZ_ERR_DEVICE, hipGetErrorString(e));
-    return MZ_OK;
+    if (int rc = glue_dtype(g, dtype)) return rc;
+    glue_dispatch(dtype, g.A, [&](auto f16, auto tiles) {
+        hipLaunchKernelGGL((k_joint_action<decltype(f16)::value, decltype(tiles)::value>), dim3(g.B), dim3(kWave), 0,
+                           g.stream, pred_logits, num_agents, g.A, current_agent, (const int *)factor, factor_cols,
+                           (const int *)actions, (long long *)joint_out);
+    });
+    return glue_end(g);
 }
 
 int mz_policy_glue_later(mz_batch *b, const void *logits, int dtype, int64_t row_stride, int num_agents,
                          int current_agent, double sampled_tau, float *probs_out, float *beta_out,
                          int32_t *later_out) {
     const char *fn = "mz_policy_glue_later";
-    int B = 0, A = 0;
-    hipStream_t stream = nullptr;
-    int rc = mz_internal_launch_info(b, &B, &A, &stream);
-    if (rc) return rc;
-    SumPlan plan{};
-    if (A > kWave && !sum_plan(A, &plan)) return glue_fail(MZ_ERR_UNSUPPORTED, fn, "action_space_size > 255");
-    if (num_agents < 1 || num_agents > kMaxLaterAgents || current_agent < 0 || current_agent >= num_agents)
+    Glue g;
+    if (int rc = glue_begin(&g, fn, b, true)) return rc;
+    if (num_agents < 1 || num_agents > kMaxGridRows || current_agent < 0 || current_agent >= num_agents)
         return glue_fail(MZ_ERR_ARG, fn, "bad agent index / count");
     if (!logits) return glue_fail(MZ_ERR_ARG, fn, "null buffer");
     if (!probs_out != !beta_out) return glue_fail(MZ_ERR_ARG, fn, "probs_out and beta_out go together");
     const int glue = probs_out ? 1 : 0, later = num_agents - 1 - current_agent;
     if (later > 0 && !later_out) return glue_fail(MZ_ERR_ARG, fn, "later_out required for later agents");
     if (glue + later == 0) return glue_fail(MZ_ERR_ARG, fn, "no output asked for");
-    if (dtype != MZ_DT_F32 && dtype != MZ_DT_F16) return glue_fail(MZ_ERR_ARG, fn, "bad dtype");
-    if (row_stride < (int64_t)num_agents * A)
+    if (int rc = glue_dtype(g, dtype)) return rc;
+    if (row_stride < (int64_t)num_agents * g.A)
         return glue_fail(MZ_ERR_ARG, fn, "logits row does not hold every agent's actions");
-    if (!(sampled_tau > 0.0)) return glue_fail(MZ_ERR_ARG, fn, "sampled_tau must be > 0");
-    const double inv = 1.0 / sampled_tau;  // as mz_policy_glue
-    const float tau_inv = (dtype == MZ_DT_F16) ? (float)(_Float16)inv : (float)inv;
-    const int use_pow = pow_mode(inv);
-    const unsigned short *hexp = half_exp_table();
-    const dim3 grid(B, glue + later);
-    if (A > kWave) {
-#define MZ_LAUNCH(T)                                                                                              \
-    if (dtype == MZ_DT_F16)                                                                                       \
-        hipLaunchKernelGGL((k_policy_glue_later_wide<true, T>), grid, dim3(kWave), 0, stream, logits,             \
-                           (long long)row_stride, num_agents, A, current_agent, glue, plan, use_pow, tau_inv,     \
-                           probs_out, beta_out, (int *)later_out, hexp);                                          \
-    else                                                                                                          \
-        hipLaunchKernelGGL((k_policy_glue_later_wide<false, T>), grid, dim3(kWave), 0, stream, logits,            \
-                           (long long)row_stride, num_agents, A, current_agent, glue, plan, use_pow, tau_inv,     \
-                           probs_out, beta_out, (int *)later_out, hexp)
-        MZ_WIDE_TILES(A, MZ_LAUNCH);
-#undef MZ_LAUNCH
-    } else if (dtype == MZ_DT_F16)
-        hipLaunchKernelGGL(k_policy_glue_later<true>, grid, dim3(kWave), 0, stream, logits, (long long)row_stride,
-                           num_agents, A, current_agent, glue, use_pow, tau_inv, probs_out, beta_out,
-                           (int *)later_out, hexp);
-    else
-        hipLaunchKernelGGL(k_policy_glue_later<false>, grid, dim3(kWave), 0, stream, logits, (long long)row_stride,
-                           num_agents, A, current_agent, glue, use_pow, tau_inv, probs_out, beta_out,
-                           (int *)later_out, hexp);
-    mz_internal_enqueued(b);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return mz_internal_fail(MZ_ERR_DEVICE, hipGetErrorString(e));
-    return MZ_OK;
+    if (int rc = glue_tau(&g, sampled_tau, dtype == MZ_DT_F16)) return rc;  // as mz_policy_glue
+    glue_dispatch(dtype, g.A, [&](auto f16, auto tiles) {
+        hipLaunchKernelGGL((k_policy_glue_later<decltype(f16)::value, decltype(tiles)::value>),
+                           dim3(g.B, glue + later), dim3(kWave), 0, g.stream, logits, (long long)row_stride,
+                           num_agents, g.plan, current_agent, glue, g.use_pow, g.tau_inv, probs_out, beta_out,
+                           (int *)later_out, g.hexp);
+    });
+    return glue_end(g);
 }
 
 int mz_joint_action_cached(mz_batch *b, const int32_t *later_pool, int slots, const int32_t *idx_x, int num_agents,
                            int current_agent, const int32_t *factor, int factor_cols, const int32_t *actions,
                            int64_t *joint_out) {
     const char *fn = "mz_joint_action_cached";
-    int B = 0, A = 0;
-    hipStream_t stream = nullptr;
-    int rc = mz_internal_launch_info(b, &B, &A, &stream);
-    if (rc) return rc;
-    if (num_agents < 1 || num_agents > kMaxLaterAgents || current_agent < 0 || current_agent >= num_agents)
+    Glue g;
+    if (int rc = glue_handle(&g, fn, b)) return rc;  // (any A: no row of actions is read)
+    if (num_agents < 1 || num_agents > kMaxGridRows || current_agent < 0 || current_agent >= num_agents)
         return glue_fail(MZ_ERR_ARG, fn, "bad agent index / count");
     if (!actions || !joint_out) return glue_fail(MZ_ERR_ARG, fn, "null buffer");
     if (current_agent > 0 && (!factor || factor_cols < current_agent))
         return glue_fail(MZ_ERR_ARG, fn, "factor must hold the previous agents' actions");
     if (current_agent + 1 < num_agents && (!later_pool || !idx_x || slots < 1))
         return glue_fail(MZ_ERR_ARG, fn, "later-action pool and idx_x required for later agents");
-    const long long n = (long long)B * num_agents;
+    const long long n = (long long)g.B * num_agents;
     hipLaunchKernelGGL(k_joint_action_cached, dim3((unsigned)((n + kCachedLanes - 1) / kCachedLanes)),
-                       dim3(kCachedLanes), 0, stream, (const int *)later_pool, slots, (const int *)idx_x, B,
+                       dim3(kCachedLanes), 0, g.stream, (const int *)later_pool, slots, (const int *)idx_x, g.B,
                        num_agents, current_agent, (const int *)factor, factor_cols, (const int *)actions,
                        (long long *)joint_out);
-    mz_internal_enqueued(b);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return mz_internal_fail(MZ_ERR_DEVICE, hipGetErrorString(e));
-    return MZ_OK;
+    return glue_end(g);
 }
 
-// the workgroups of a joint glue launch, one per (root, agent); 0 when they do not fit a grid
-static unsigned joint_grid(int B, int num_agents) {
-    const long long n = (long long)B * num_agents;
-    return (n < 1 || n > 0x7fffffffll) ? 0u : (unsigned)n;
-}
-
+// The joint glue: k_policy_glue / k_root_glue with an agent per grid row.  One lane per action: joint
+// trees take no more (include/mzmcts.h).
 int mz_policy_glue_joint(mz_batch *b, const void *logits, int dtype, int64_t row_stride, int num_agents,
                          double sampled_tau, float *probs_out, float *beta_out) {
     const char *fn = "mz_policy_glue_joint";
-    int B = 0, A = 0;
-    hipStream_t stream = nullptr;
-    int rc = mz_internal_launch_info(b, &B, &A, &stream);
-    if (rc) return rc;
-    if (A > kWave)  // (one lane per action; joint trees take no more, include/mzmcts.h)
-        return glue_fail(MZ_ERR_UNSUPPORTED, fn, "action_space_size > 64");
-    if (num_agents < 1 || !joint_grid(B, num_agents)) return glue_fail(MZ_ERR_ARG, fn, "bad agent count");
+    Glue g;
+    if (int rc = glue_begin(&g, fn, b, false)) return rc;
+    if (num_agents < 1 || num_agents > kMaxGridRows) return glue_fail(MZ_ERR_ARG, fn, "bad agent count");
     if (!logits || !probs_out || !beta_out) return glue_fail(MZ_ERR_ARG, fn, "null buffer");
-    if (dtype != MZ_DT_F32 && dtype != MZ_DT_F16) return glue_fail(MZ_ERR_ARG, fn, "bad dtype");
-    if (row_stride < (int64_t)num_agents * A)
+    if (int rc = glue_dtype(g, dtype)) return rc;
+    if (row_stride < (int64_t)num_agents * g.A)
         return glue_fail(MZ_ERR_ARG, fn, "logits row does not hold every agent's actions");
-    if (!(sampled_tau > 0.0)) return glue_fail(MZ_ERR_ARG, fn, "sampled_tau must be > 0");
-    const double inv = 1.0 / sampled_tau;  // as mz_policy_glue
-    const float tau_inv = (dtype == MZ_DT_F16) ? (float)(_Float16)inv : (float)inv;
-    const int use_pow = pow_mode(inv);
-    const unsigned short *hexp = half_exp_table();
-    const dim3 grid(joint_grid(B, num_agents));
-    if (dtype == MZ_DT_F16)
-        hipLaunchKernelGGL(k_policy_glue_joint<true>, grid, dim3(kWave), 0, stream, logits, (long long)row_stride,
-                           num_agents, A, use_pow, tau_inv, probs_out, beta_out, hexp);
-    else
-        hipLaunchKernelGGL(k_policy_glue_joint<false>, grid, dim3(kWave), 0, stream, logits, (long long)row_stride,
-                           num_agents, A, use_pow, tau_inv, probs_out, beta_out, hexp);
-    mz_internal_enqueued(b);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return mz_internal_fail(MZ_ERR_DEVICE, hipGetErrorString(e));
-    return MZ_OK;
+    if (int rc = glue_tau(&g, sampled_tau, dtype == MZ_DT_F16)) return rc;  // as mz_policy_glue
+    return launch_policy_glue(g, dtype, num_agents, logits, row_stride, 0, probs_out, beta_out);
 }
 
 int mz_root_glue_joint(mz_batch *b, const void *logits, int dtype, int64_t row_stride, int num_agents,
                        const int32_t *legal, int64_t legal_stride, const float *noises, double noise_eps,
                        double sampled_tau, float *probs_out, float *beta_out, float *noises_out) {
     const char *fn = "mz_root_glue_joint";
-    int B = 0, A = 0;
-    hipStream_t stream = nullptr;
-    int rc = mz_internal_launch_info(b, &B, &A, &stream);
-    if (rc) return rc;
-    if (A > kWave)  // (one lane per action; joint trees take no more, include/mzmcts.h)
-        return glue_fail(MZ_ERR_UNSUPPORTED, fn, "action_space_size > 64");
-    if (num_agents < 1 || !joint_grid(B, num_agents)) return glue_fail(MZ_ERR_ARG, fn, "bad agent count");
+    Glue g;
+    if (int rc = glue_begin(&g, fn, b, false)) return rc;
+    if (num_agents < 1 || num_agents > kMaxGridRows) return glue_fail(MZ_ERR_ARG, fn, "bad agent count");
     if (!logits || !noises || !probs_out || !beta_out || !noises_out) return glue_fail(MZ_ERR_ARG, fn, "null buffer");
-    if (dtype != MZ_DT_F32 && dtype != MZ_DT_F16) return glue_fail(MZ_ERR_ARG, fn, "bad dtype");
-    if (row_stride < (int64_t)num_agents * A)
+    if (int rc = glue_dtype(g, dtype)) return rc;
+    if (row_stride < (int64_t)num_agents * g.A)
         return glue_fail(MZ_ERR_ARG, fn, "logits row does not hold every agent's actions");
-    if (legal && legal_stride < (int64_t)num_agents * A)
+    if (legal && legal_stride < (int64_t)num_agents * g.A)
         return glue_fail(MZ_ERR_ARG, fn, "legal rows hold fewer than num_agents * A");
-    if (!(sampled_tau > 0.0)) return glue_fail(MZ_ERR_ARG, fn, "sampled_tau must be > 0");
-    const double inv = 1.0 / sampled_tau;  // as mz_root_glue: beta is a float32 array
-    const float tau_inv = (float)inv;
-    const int use_pow = pow_mode(inv);
-    const double ome = 1.0 - noise_eps;  // (Python float arithmetic)
-    const unsigned short *hexp = half_exp_table();
-    const dim3 grid(joint_grid(B, num_agents));
-    if (dtype == MZ_DT_F16)
-        hipLaunchKernelGGL(k_root_glue_joint<true>, grid, dim3(kWave), 0, stream, logits, (long long)row_stride,
-                           num_agents, A, (const int *)legal, (long long)legal_stride, noises, ome, noise_eps,
-                           use_pow, tau_inv, probs_out, beta_out, noises_out, hexp);
-    else
-        hipLaunchKernelGGL(k_root_glue_joint<false>, grid, dim3(kWave), 0, stream, logits, (long long)row_stride,
-                           num_agents, A, (const int *)legal, (long long)legal_stride, noises, ome, noise_eps,
-                           use_pow, tau_inv, probs_out, beta_out, noises_out, hexp);
-    mz_internal_enqueued(b);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return mz_internal_fail(MZ_ERR_DEVICE, hipGetErrorString(e));
-    return MZ_OK;
+    if (int rc = glue_tau(&g, sampled_tau, false)) return rc;  // as mz_root_glue: beta is a float32 array
+    return launch_root_glue(g, dtype, num_agents, logits, row_stride, 0, legal, legal_stride, noises, noise_eps,
+                            probs_out, beta_out, noises_out);
 }
 
 int mz_policy_glue(mz_batch *b, const void *logits, int dtype, int64_t row_stride, int64_t col_offset,
@@ -1444,12 +1200,13 @@ int mz_inverse_sum_plan(int S, int n, int *vectorized, int *block_width) {
 
 int mz_wide_sum_plan(int n, int32_t *starts, int32_t *lens, int32_t *num_blocks) {
     if (!starts || !lens || !num_blocks) return mz_internal_fail(MZ_ERR_ARG, "mz_wide_sum_plan: null argument");
-    SumPlan plan{};
-    if (!sum_plan(n, &plan)) return mz_internal_fail(MZ_ERR_UNSUPPORTED, "mz_wide_sum_plan: n outside 1..255");
+    if (n < 1 || n > kWideMax) return mz_internal_fail(MZ_ERR_UNSUPPORTED, "mz_wide_sum_plan: n outside 1..255");
+    const unsigned plan = sum_plan(n);
     int k = 0;
-    for (int i = 0; i < kMaxBlocks; ++i) {
-        starts[i] = (int32_t)(plan.start >> (8 * i) & 0xffu);
-        lens[i] = (int32_t)(plan.len >> (8 * i) & 0xffu);
+    for (int i = 0, start = 0; i < kMaxBlocks; ++i) {
+        lens[i] = (int32_t)(plan >> (8 * i) & 0xffu);
+        starts[i] = lens[i] ? start : 0;
+        start += lens[i];
         if (lens[i]) ++k;
     }
     *num_blocks = k;

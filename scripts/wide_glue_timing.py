@@ -1,5 +1,7 @@
-"""Per-launch time of the driver glue's policy and joint-action kernels, narrow and wide entry points
-(include/mzdriver.h), on cuda:0.  A record, not a gate: profiles/wide_glue/README.md holds the numbers.
+"""Per-launch time of the driver glue's entry points (include/mzdriver.h) on cuda:0: policy, root and
+joint-action glue through the narrow, wide, joint and later-action entry points, at the workload's own
+action counts (9, 64) and past one tile (65, 128, 255).  A record, not a gate:
+profiles/wide_glue/README.md and profiles/glue_unify/README.md hold the numbers.
 
 Each configuration is a window of `--launches` back-to-back launches on the handle's stream between
 two device events, after a warm-up window; the windows of all configurations alternate `--repeats`
@@ -7,7 +9,9 @@ times, and the per-launch time is window / launches (median, minimum and maximum
 Two windows per configuration: "eager" enqueues the launches from Python, so the host's enqueue rate
 bounds it from below; "graph" replays a captured graph of the same launches, which is how a search
 runs them (mazero_amd.mcts_sampled).
-B = 256 roots, N = 3 agents, float32 and float16 logits, sampled_tau = 1.
+B = 256 roots, N = 3 agents, float32 and float16 logits, sampled_tau = 1; the root glue with a legal
+mask (about 30 % zeros) and noise_eps = 0.25; mz_policy_glue_later as the first agent's (two argmax
+roles); the joint entry points over all 3 agents.
 
     python scripts/wide_glue_timing.py [--launches 2000] [--repeats 7] [--out FILE.json]
 """
@@ -24,7 +28,15 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 B, N = 256, 3
 CONFIGS = [  # (entry point, A)
+    ("mz_policy_glue", 9),
     ("mz_policy_glue", 64),
+    ("mz_root_glue", 9),
+    ("mz_root_glue", 64),
+    ("mz_policy_glue_joint", 9),
+    ("mz_root_glue_joint", 9),
+    ("mz_policy_glue_later", 9),
+    ("mz_policy_glue_later", 255),
+    ("mz_joint_action", 9),
     ("mz_policy_glue_wide", 64),
     ("mz_policy_glue_wide", 65),
     ("mz_policy_glue_wide", 128),
@@ -50,12 +62,28 @@ def make_launch(fn_name, A, dtype, handles):
     rng = np.random.default_rng(A)
     logits = torch.from_numpy(rng.standard_normal((B, N, A)).astype(dtype)).to(dev)
     fn = getattr(lib, fn_name)
-    if fn_name.startswith("mz_policy_glue"):
+    rows = N if fn_name.endswith("_joint") else 1  # agents per launch
+    p = lambda t: C.c_void_p(t.data_ptr())  # noqa: E731
+    if fn_name.startswith("mz_root_glue"):
+        noise = torch.from_numpy(rng.dirichlet([0.3] * A, (B, rows)).astype(np.float32)).to(dev)
+        legal = (rng.random((B, rows, A)) >= 0.3).astype(np.int32)
+        legal[..., 0] = np.where(legal.sum(-1) == 0, 1, legal[..., 0])
+        legal = torch.from_numpy(legal).to(dev)
+        outs = [torch.empty(B, rows, A, device=dev) for _ in range(3)]
+        where = (N * A, N) if rows > 1 else (N * A, A)  # (row stride, agents) / (row stride, col_offset)
+        args = (h, p(logits), code, *where, p(legal), rows * A, p(noise), 0.25, 1.0, *[p(o) for o in outs])
+        keep = (logits, noise, legal, outs)
+    elif fn_name == "mz_policy_glue_later":
         probs, beta = torch.empty(B, A, device=dev), torch.empty(B, A, device=dev)
-        args = (h, C.c_void_p(logits.data_ptr()), code, N * A, A, 1.0, C.c_void_p(probs.data_ptr()),
-                C.c_void_p(beta.data_ptr()))
+        later = torch.empty(B, N, dtype=torch.int32, device=dev)
+        args = (h, p(logits), code, N * A, N, 0, 1.0, p(probs), p(beta), p(later))
+        keep = (logits, probs, beta, later)
+    elif fn_name.startswith("mz_policy_glue"):
+        probs, beta = torch.empty(B, rows, A, device=dev), torch.empty(B, rows, A, device=dev)
+        where = (N * A, N) if rows > 1 else (N * A, A)
+        args = (h, p(logits), code, *where, 1.0, p(probs), p(beta))
         keep = (logits, probs, beta)
-    else:  # current agent 0: the argmax of the two later agents' rows
+    else:  # mz_joint_action(_wide), current agent 0: the argmax of the two later agents' rows
         act = torch.zeros(B, dtype=torch.int32, device=dev)
         fac = torch.zeros(B, 1, dtype=torch.int32, device=dev)
         joint = torch.empty(B, N, dtype=torch.int64, device=dev)

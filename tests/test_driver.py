@@ -202,8 +202,9 @@ def test_numpy_half_power_is_correctly_rounded(tau):
 
 @pytest.mark.gpu
 @pytest.mark.parametrize("dtype", ["float32", "float16"])
-@pytest.mark.parametrize("A", [3, 9, 15, 36, 64])
+@pytest.mark.parametrize("A", [1, 3, 7, 8, 9, 15, 36, 64])
 def test_policy_glue_matches_numpy(dtype, A):
+    """A = 7 is numpy's longest sequential row sum, A = 8 its first 8-accumulator sum (no tail)."""
     import torch
 
     from mazero_amd._capi import MZ_DT_F16, MZ_DT_F32, check
@@ -979,11 +980,12 @@ def test_double_to_half_rounding_restatement():
 
 @pytest.mark.gpu
 @pytest.mark.parametrize("dtype", ["float32", "float16"])
-@pytest.mark.parametrize("A", [3, 9, 15, 36, 64])
+@pytest.mark.parametrize("A", [1, 3, 7, 8, 9, 15, 36, 64])
 def test_root_glue_matches_host_root_inputs(dtype, A):
     """mz_root_glue against the host root preprocessing (SampledMCTS.root_inputs, the reference's
     numpy expressions, pinned to the reference driver by the driver_*.npz fixtures), bit for bit:
-    legal masks as int64 and bool with zeros, none; noise on and off; extreme logits."""
+    legal masks as int64 and bool with zeros, none; noise on and off; extreme logits.  A = 1, 7, 8:
+    both sides of the row sum's switch from numpy's sequential sum to its 8 accumulators."""
     import torch
 
     from mazero_amd._capi import MZ_DT_F16, MZ_DT_F32, check

@@ -202,9 +202,10 @@ def _glue_logits(rng, N, A, dtype, pad=3):
 @pytest.mark.parametrize("dtype", ["float32", "float16"])
 @pytest.mark.parametrize("A", [1, 3, 9, 11, 64])
 def test_policy_glue_joint_is_the_narrow_kernel_per_agent(A, dtype):
-    """mz_policy_glue_joint, one launch, against N launches of mz_policy_glue stacked and against the
-    numpy expression (mcts_sampled.py:158-161), for N in {2, 3, 8}, B = 5, row stride N * A + 3, with
-    rows holding a NaN, -inf, +inf and all-equal logits; tau 1 and 0.5."""
+    """mz_policy_glue_joint, one launch (mz_policy_glue's kernel with an agent per grid row), against N
+    launches of mz_policy_glue stacked and against the numpy expression (mcts_sampled.py:158-161), for
+    N in {2, 3, 8}, B = 5, row stride N * A + 3, with rows holding a NaN, -inf, +inf and all-equal
+    logits; tau 1 and 0.5."""
     import torch
 
     from mazero_amd._capi import check
@@ -243,9 +244,10 @@ def test_policy_glue_joint_is_the_narrow_kernel_per_agent(A, dtype):
 @pytest.mark.parametrize("dtype", ["float32", "float16"])
 @pytest.mark.parametrize("A", [1, 3, 9, 11, 64])
 def test_root_glue_joint_is_the_narrow_kernel_per_agent(A, dtype):
-    """mz_root_glue_joint against N launches of mz_root_glue on the agent's own logits, legal and noise
-    columns: with and without `legal` (at least one legal action per (root, agent)), eps in {0, 0.25},
-    tau in {1, 0.5}, N in {2, 3, 8}, B = 5, row stride N * A + 3."""
+    """mz_root_glue_joint (mz_root_glue's kernel with an agent per grid row) against N launches of
+    mz_root_glue on the agent's own logits, legal and noise columns: with and without `legal` (at least
+    one legal action per (root, agent)), eps in {0, 0.25}, tau in {1, 0.5}, N in {2, 3, 8}, B = 5, row
+    stride N * A + 3."""
     import torch
 
     from mazero_amd._capi import check

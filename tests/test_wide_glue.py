@@ -1,8 +1,9 @@
 """The driver glue for action spaces of 65..255 (include/mzdriver.h: mz_policy_glue_wide,
 mz_root_glue_wide, mz_joint_action_wide) and SampledMCTS(..., wide_actions=True).
 
-CPU tests pin what the wide kernels rely on: the launcher's block plan of a row sum (mz_wide_sum_plan)
-reproduces numpy's pairwise np.sum for every row length up to 255, and the constructor's opt-in.
+CPU tests pin what the glue kernels rely on at every width: the block plan of a row sum (one function
+for host and device, mz_wide_sum_plan on the host) reproduces numpy's pairwise np.sum for every row
+length up to 255, and the constructor's opt-in.
 GPU tests compare the kernels with the numpy expressions of the reference driver
 (mcts_sampled.py:64-100,116-147,156-161) bit for bit, the _wide entry points with the narrow ones at
 A <= 64, and whole searches with the oracle driver on the CPU port.
@@ -37,7 +38,8 @@ def _plan(lib, n):
 
 def _block_sum(X):
     """numpy's pairwise-sum base case (n <= 128) of every row of the float32 array X [R, n]: what one
-    group of 8 lanes and its first lane compute in np_row_sum_wide (mzdriver.hip)."""
+    group of 8 lanes and its first lane compute in np_row_sum (mzdriver.hip), at every tile count;
+    n < 8 (only a row of A < 8 is such a block) is the sequential sum its first lane's tail loop takes."""
     n = X.shape[1]
     if n < 8:
         r = np.zeros(X.shape[0], np.float32)
@@ -56,7 +58,7 @@ def _block_sum(X):
 
 
 def _planned_sum(X, plan):
-    """The row sums of the float32 array X as the wide kernels take them: base-case blocks, joined
+    """The row sums of the float32 array X as the glue kernels take them: base-case blocks, joined
     from the right."""
     assert X.dtype == np.float32
     sums = [_block_sum(X[:, s:s + ln]) for s, ln in plan]
@@ -84,7 +86,7 @@ def test_sum_plan_shape(product_lib):
             assert s + ln == s2
         assert all(s % 8 == 0 and 1 <= ln <= 128 for s, ln in plan)
         assert len(plan) == (1 if n <= 128 else 2 if n <= 248 else 3), n
-        if n > 64:  # what the wide kernels run on: no block takes numpy's n < 8 path
+        if n > 64:  # past one tile no block takes numpy's n < 8 path: only a row of A < 8 does
             assert all(ln >= 64 for _, ln in plan), n
     assert _plan(product_lib, 129) == [(0, 64), (64, 65)]
     assert _plan(product_lib, 200) == [(0, 96), (96, 104)]
@@ -209,11 +211,13 @@ def _code(dtype):
 
 def _policy_logits(rng, N, A, cur, dtype):
     """B = 6 rows of the current agent: a NaN in the last tile, -inf entries, constant logits, three
-    random rows of different scales."""
+    random rows of different scales, one of them with a +inf (its softmax is inf - inf: numpy's NaN
+    for a row without a NaN of its own)."""
     logits = (rng.standard_normal((B, N, A)) * np.array([1, 1, 1, 0.1, 4, 30]).reshape(B, 1, 1)).astype(dtype)
     logits[0, cur, A - 1] = np.nan
     logits[1, cur, rng.choice(A, size=A // 3, replace=False)] = -np.inf
     logits[2, cur, :] = logits[2, cur, 0]
+    logits[4, cur, A // 2] = np.inf
     return logits
 
 
@@ -373,9 +377,10 @@ def test_joint_action_wide_matches_numpy(A, dtype):
 
 @pytest.mark.gpu
 @pytest.mark.parametrize("dtype", ["float32", "float16"])
-@pytest.mark.parametrize("A", [9, 64])
+@pytest.mark.parametrize("A", [7, 9, 64])
 def test_wide_entry_points_equal_narrow_up_to_64(A, dtype):
-    """A <= 64: the _wide entry points launch the narrow kernels; same bytes on the same inputs."""
+    """A <= 64: the _wide entry points launch the kernels of the narrow ones (the T = 1 instantiations);
+    same bytes on the same inputs.  A = 7: numpy's sequential row sum."""
     from mazero_amd.mcts_sampled import SampledMCTS
     from mazero_amd.nets import SearchConfig
 
