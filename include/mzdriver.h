@@ -72,6 +72,28 @@ int mz_get_active_roots(mz_batch *b, int *n);
 int mz_set_root_offset(mz_batch *b, int root_offset);
 int mz_get_root_offset(mz_batch *b, int *root_offset);
 
+/* Seed segments: one (random_seed, root_offset) pair per contiguous run of the handle's trees, so that
+ * several reference searches -- each with its own np_random.choice(256) seed (mcts_sampled.py:89), each
+ * seeding tree i from its own row 0 (cnode.cpp:574) -- ride on one handle and one recorded loop
+ * (mazero_amd.mcts_sampled batch_search_many).  From the next mz_prepare / mz_prepare_select on, tree t
+ * with first_tree[g] <= t < first_tree[g + 1] (the last segment runs to root_num) is seeded with
+ * seeds[g] * 2333 + root_offsets[g] + (t - first_tree[g]) mod 2^32: the tree of a fresh handle created
+ * with (seeds[g], root_offsets[g]) at row t - first_tree[g].  The values live in a per-tree device table,
+ * an allocation of its own made by the first call and written by a kernel on the handle's stream; the
+ * prepare kernels' segmented instantiations (k_prepare1_seg, k_prepare_seg) read it, also when replayed
+ * from a captured graph, so changing the segments between replays changes the next search.  Like
+ * mz_reseed it is meant to be called outside a graph capture; a graph recorded without segments does not
+ * read the table.  n = 0 returns the handle to its (seed, root_offset) words, which mz_reseed and
+ * mz_set_root_offset keep writing meanwhile.  A handle that never sets segments launches what it always
+ * launched.  The call leaves the active-root count, the trees and a ready packed readback alone.
+ * first_tree[0] = 0, first_tree strictly increasing and below root_num, 0 <= root_offsets[g] and
+ * root_offsets[g] + the segment's tree count <= INT32_MAX, else MZ_ERR_ARG (nothing changes).
+ * mz_get_seed_segments writes the host's copy: *n segments, the first min(*n, cap) of them into the
+ * arrays (which may be NULL when cap = 0). */
+int mz_set_seed_segments(mz_batch *b, int n, const int32_t *first_tree, const uint32_t *seeds,
+                         const int32_t *root_offsets);
+int mz_get_seed_segments(mz_batch *b, int cap, int *n, int32_t *first_tree, uint32_t *seeds, int32_t *root_offsets);
+
 /* Tell the handle that its trees were changed by work it did not enqueue itself -- the replay of
  * a captured graph of mz_* calls -- so that host-side readback caches are dropped.  (Captured
  * launches read the seed and every input from device memory, so a replay after mz_reseed and

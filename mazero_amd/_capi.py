@@ -116,6 +116,11 @@ DRIVER_SIGNATURES = {
     "mz_get_active_roots": (_i, [_p, C.POINTER(_i)]),
     "mz_set_root_offset": (_i, [_p, _i]),
     "mz_get_root_offset": (_i, [_p, C.POINTER(_i)]),
+    # per-segment tree seeds: (handle, n, first_tree[n], seeds[n], root_offsets[n]); the getter takes the
+    # arrays' capacity and returns n
+    "mz_set_seed_segments": (_i, [_p, _i, C.POINTER(C.c_int32), C.POINTER(C.c_uint32), C.POINTER(C.c_int32)]),
+    "mz_get_seed_segments": (_i, [_p, _i, C.POINTER(_i), C.POINTER(C.c_int32), C.POINTER(C.c_uint32),
+                                  C.POINTER(C.c_int32)]),
     "mz_policy_glue": (_i, [_p, _p, _i, _i64, _i64, C.c_double, _p, _p]),
     "mz_root_glue": (_i, [_p, _p, _i, _i64, _i64, _p, _i64, _p, C.c_double, C.c_double, _p, _p, _p]),
     "mz_joint_action": (_i, [_p, _p, _i, _i, _i, _p, _i, _p, _p]),

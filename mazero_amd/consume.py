@@ -271,13 +271,15 @@ class ReanalyzePolicy(NamedTuple):
     root_pred_values: torch.Tensor  # network_output.value as [B', 1]
 
 
-def reanalyze_policy_targets(mcts, model, network_output, legal_actions_lst, policy_mask, device=None
-                             ) -> ReanalyzePolicy:
+def reanalyze_policy_targets(mcts, model, network_output, legal_actions_lst, policy_mask, device=None,
+                             _first=None) -> ReanalyzePolicy:
     """`_prepare_policy_re` after the initial inference (reanalyze_worker.py:266-366): per agent
     a search (add_noise=True, sampled_tau=1.0) conditioned on the earlier agents' chosen actions,
     action = argmax(marginal visits * legal), and the product of the agents' marginal
     distributions at the chosen actions.  Requires num_simulations >= 1: with no visits the
-    reference draws the action from np_random instead."""
+    reference draws the action from np_random instead.
+    (`_first` = (out, lo, hi, legal): agent 0's search already ran as rows [lo, hi) of the merged search
+    `out`, whose rows have the agent-0 legal actions `legal`: reanalyze_batch_targets.)"""
     if mcts.config.num_simulations < 1:
         raise ValueError("reanalyze_policy_targets needs num_simulations >= 1")
     hidden = network_output.hidden_state
@@ -291,6 +293,19 @@ def reanalyze_policy_targets(mcts, model, network_output, legal_actions_lst, pol
     value0 = None
     for k in range(N):
         factor = current[:, :k] if k > 0 else None
+        if k == 0 and _first is not None:
+            # the kernel runs over the merged handle's rows; this search's are sliced out (rows are
+            # independent: its own rows get what a launch over them alone writes)
+            whole, lo, hi, legal_whole = _first
+            value0 = whole.value[lo:hi].reshape(B, 1)
+            rows = whole.value.shape[0]
+            a_whole = torch.empty(rows, dtype=torch.int32, device=dev)
+            prob_whole = torch.ones(rows, dtype=torch.float64, device=dev)
+            with torch.cuda.device(dev):
+                marginal_policy(whole, MZ_MARGINAL_ARGMAX, a_whole, prob_whole, legal=legal_whole)
+            current[:, 0] = a_whole[lo:hi]
+            prob = prob_whole[lo:hi].clone()
+            continue
         out = mcts.batch_search_device(model, network_output, k, factor, N, legal_np, device, add_noise=True,
                                        sampled_tau=1.0)
         if k == 0:
@@ -481,8 +496,8 @@ def _rows_of(rows, total):
 
 def reanalyze_value_targets(mcts, model, network_output, legal_actions_lst, *, rewards, pos, traj_len, td_steps,
                             discount: float, num_unroll_steps: int, td_max: Optional[int] = None,
-                            use_root_value: bool = True, use_pred_value: bool = False, rows=None, device=None
-                            ) -> Tuple[torch.Tensor, torch.Tensor]:
+                            use_root_value: bool = True, use_pred_value: bool = False, rows=None, device=None,
+                            _search=None) -> Tuple[torch.Tensor, torch.Tensor]:
     """`_prepare_reward_value_re` after the initial inference (reanalyze_worker.py:116-164) ->
     (batch_rewards, batch_values), float64 [G, U+1] device tensors.
 
@@ -499,7 +514,9 @@ def reanalyze_value_targets(mcts, model, network_output, legal_actions_lst, *, r
     maximum; pass config.td_steps to keep one table size).
 
     rows = (lo, hi): `network_output` holds rows [lo, hi) only (a rank's share, with `mcts` built
-    for that root shard); the result is then flat, float64 [hi - lo] each."""
+    for that root shard); the result is then flat, float64 [hi - lo] each.
+    (`_search` = (out, lo, hi): the agent-0 search already ran as rows [lo, hi) of the merged search `out`:
+    reanalyze_batch_targets.)"""
     U = int(num_unroll_steps)
     hidden = network_output.hidden_state
     dev = hidden.device if isinstance(hidden, torch.Tensor) and hidden.is_cuda else torch.device(device or "cuda")
@@ -511,7 +528,10 @@ def reanalyze_value_targets(mcts, model, network_output, legal_actions_lst, *, r
     td_steps_lst = [np.intc(x) for x in np.repeat(ti.td, U + 1)]
     td_pow = torch.from_numpy(np.ascontiguousarray(np.power(discount, td_steps_lst)[lo:hi], dtype=np.float64)).to(dev)
     tb = None
-    if use_root_value:
+    if use_root_value and _search is not None:
+        tb = _tree(_search[0])
+        value = _search[0].value[_search[1]:_search[2]].reshape(-1)  # (a contiguous row range: no copy)
+    elif use_root_value:
         legal_np = np.asarray(legal_actions_lst)
         out = mcts.batch_search_device(model, network_output, 0, None, legal_np.shape[1], legal_np, device,
                                        add_noise=True, sampled_tau=1.0)
@@ -525,6 +545,37 @@ def reanalyze_value_targets(mcts, model, network_output, legal_actions_lst, *, r
         raise ValueError(f"{value.shape[0]} values for {n} rows")
     r, v = _launch_value_targets(tb, dev, MZ_VALUE_RE, ti, lo, hi, value, td_pow, None, False)
     return (r, v) if rows is not None else (r.reshape(ti.G, U + 1), v.reshape(ti.G, U + 1))
+
+
+def reanalyze_batch_targets(mcts, model, value_output, value_legal, policy_output, policy_legal, policy_mask, *,
+                            rewards, pos, traj_len, td_steps, discount: float, num_unroll_steps: int,
+                            td_max: Optional[int] = None, rows=None, device=None
+                            ) -> Tuple[torch.Tensor, torch.Tensor, ReanalyzePolicy]:
+    """A reanalyze batch's targets, make_batch of core/reanalyze_worker.py: `reanalyze_value_targets(mcts,
+    model, value_output, value_legal, ...)` followed by `reanalyze_policy_targets(mcts, model,
+    policy_output, policy_legal, policy_mask)` -> (batch_rewards, batch_values, ReanalyzePolicy), with the
+    value search (:121-129) and the first policy search (:284-294) -- both agent 0, factor None,
+    add_noise=True, sampled_tau=1.0, on other observations -- run as one
+    `mcts.batch_search_many_device`: one search latency less per batch.  The outputs and the state of
+    `mcts.np_random` equal those of the two calls made one after the other, on the guarantee of
+    SampledMCTS.batch_search_many.  mz_value_targets reads the value segment's rows of the merged output;
+    mz_marginal_policy runs over the handle's rows and the policy segment is sliced out; the later
+    agents' searches are those of reanalyze_policy_targets."""
+    if mcts.config.num_simulations < 1:
+        raise ValueError("reanalyze_batch_targets needs num_simulations >= 1")
+    vl, pl = np.asarray(value_legal), np.asarray(policy_legal)
+    N = pl.shape[1]
+    whole, bounds = mcts.batch_search_many_device(model, [value_output, policy_output], 0, [None, None], N,
+                                                  [vl, pl], device, add_noise=True, sampled_tau=1.0)
+    dev = whole.value.device
+    r, v = reanalyze_value_targets(mcts, model, value_output, vl, rewards=rewards, pos=pos, traj_len=traj_len,
+                                   td_steps=td_steps, discount=discount, num_unroll_steps=num_unroll_steps,
+                                   td_max=td_max, use_root_value=True, rows=rows, device=device,
+                                   _search=(whole, bounds[0], bounds[1]))
+    legal_whole = torch.cat([_dev_i32(vl[:, 0, :], dev), _dev_i32(pl[:, 0, :], dev)], 0)
+    pol = reanalyze_policy_targets(mcts, model, policy_output, pl, policy_mask, device,
+                                   _first=(whole, bounds[1], bounds[2], legal_whole))
+    return r, v, pol
 
 
 def value_targets_non_re(rewards, stored, pos, traj_len, *, td_steps: int, discount: float, num_unroll_steps: int,

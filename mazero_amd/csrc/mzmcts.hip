@@ -158,6 +158,13 @@ __device__ __forceinline__ unsigned seed_value(const Dev &d, int t) {
     const uint2 s = *(const uint2 *)d.seed();
     return s.x * 2333u + s.y + (unsigned)t;
 }
+// The same under per-segment seeds (mz_set_seed_segments): entry t of the handle's per-tree table holds
+// {seeds[g], root_offsets[g] - first_tree[g]} of tree t's segment g, so the value is again one aligned
+// 8-byte load, at an address that follows from the workgroup id, and the same expression.
+__device__ __forceinline__ unsigned seed_value_seg(const uint2 *__restrict__ seg, int t) {
+    const uint2 s = seg[t];
+    return s.x * 2333u + s.y + (unsigned)t;
+}
 
 struct StepArgs {
     int hsx;
@@ -1471,7 +1478,10 @@ __global__ __launch_bounds__(256) void k_seed_table(unsigned *cp, unsigned n) {
     for (unsigned i = threadIdx.x; i < nrows * (kSeedRow / 4); i += 256u) dst[i] = src[i];
 }
 
-__global__ __launch_bounds__(256) void k_prepare(const Params *__restrict__ prm, PrepArgs a) {
+// (the body of k_prepare and k_prepare_seg; SEG: the seed value from the per-tree table `seg`)
+template <bool SEG>
+__device__ __forceinline__ void prepare_body(const Params *__restrict__ prm, const PrepArgs a,
+                                             const uint2 *__restrict__ seg) {
     const Geo g = prm->g;
     const Dev d = prm->d;
     __shared__ unsigned mt[kMtN];
@@ -1486,7 +1496,7 @@ __global__ __launch_bounds__(256) void k_prepare(const Params *__restrict__ prm,
     // error also stays in its header, and every later kernel re-reports the errors of dead trees,
     // so an error raised by another block before this store is not lost.
     if (t == 0 && tid == 0) *d.err() = 0;
-    const unsigned seed_v = seed_value(d, t);
+    const unsigned seed_v = SEG ? seed_value_seg(seg, t) : seed_value(d, t);
     const unsigned *cp = prm->cp;
     if (cp && seed_v < prm->cp_n) {
         // the seeding chain from the checkpoints: lane j replays words 16j .. 16j + 15
@@ -1675,6 +1685,16 @@ __global__ __launch_bounds__(256) void k_prepare(const Params *__restrict__ prm,
         if (err) atomicOr(d.err(), err);
     }
     span_close(0, rt0);
+}
+
+__global__ __launch_bounds__(256) void k_prepare(const Params *__restrict__ prm, PrepArgs a) {
+    prepare_body<false>(prm, a, nullptr);
+}
+// k_prepare on a handle with per-segment seeds (mz_set_seed_segments): the same launch with the
+// per-tree seed table behind the arguments
+__global__ __launch_bounds__(256) void k_prepare_seg(const Params *__restrict__ prm, PrepArgs a,
+                                                     const uint2 *__restrict__ seg) {
+    prepare_body<true>(prm, a, seg);
 }
 
 // Bootstrap recurrence b = r + disc * b (cnode.cpp:448) over `n` levels, lane-parallel: level
@@ -5461,9 +5481,11 @@ static_assert(sizeof(Prep1IO) == 64, "k_prepare1: one 64-byte argument line");
 constexpr int kPrep1Waves = 5;
 constexpr int kPrep1Words = kNxt + 2;  // engine words the root wave computes itself: the draw's two, then nxt
 static_assert(kPrep1Words <= kWave && kPrep1Words + 397 <= kMtN && kPrep1Words <= 227, "root wave's engine words");
-__global__ __launch_bounds__(kPrep1Waves *kWave) void k_prepare1(char *base, const float *reward, const float *value,
-                                                                 const float *policy, const float *beta,
-                                                                 const float *noise, int bak, int pps, Prep1IO io) {
+// (the body of k_prepare1 and k_prepare1_seg; SEG: the seed value from the per-tree table `seg`)
+template <bool SEG>
+__device__ __forceinline__ void prepare1_body(char *base, const float *reward, const float *value,
+                                              const float *policy, const float *beta, const float *noise, int bak,
+                                              int pps, const Prep1IO io, const uint2 *__restrict__ seg) {
     __shared__ unsigned mt[kMtN];
     __shared__ unsigned mt2[kMtN];
     // the root wave's scratch for cdf_bcast (A > 16).  cdf_long issues its last three reads together,
@@ -5600,7 +5622,7 @@ __global__ __launch_bounds__(kPrep1Waves *kWave) void k_prepare1(char *base, con
     // ======== waves 1 .. 4: the seeding (wave 1) and the twist ========
     const int k = (int)threadIdx.x - kWave;
     if (wv == 1) {
-        const unsigned seed_v = seed_value(d, t);
+        const unsigned seed_v = SEG ? seed_value_seg(seg, t) : seed_value(d, t);
         const unsigned *cp = io.cp;
         if (cp && seed_v < io.cp_n) {
             // the seeding chain from the checkpoints: lane j replays words 16j .. 16j + 15
@@ -5669,6 +5691,39 @@ __global__ __launch_bounds__(kPrep1Waves *kWave) void k_prepare1(char *base, con
         nxt = tmp;
     }
     if (wv == 1) span_end(0, 2);
+}
+
+__global__ __launch_bounds__(kPrep1Waves *kWave) void k_prepare1(char *base, const float *reward, const float *value,
+                                                                 const float *policy, const float *beta,
+                                                                 const float *noise, int bak, int pps, Prep1IO io) {
+    prepare1_body<false>(base, reward, value, policy, beta, noise, bak, pps, io, nullptr);
+}
+// k_prepare1 on a handle with per-segment seeds (mz_set_seed_segments): the same launch with the
+// per-tree seed table behind the argument line, which wave 1 reads in place of the seed words
+__global__ __launch_bounds__(kPrep1Waves *kWave) void k_prepare1_seg(char *base, const float *reward,
+                                                                     const float *value, const float *policy,
+                                                                     const float *beta, const float *noise, int bak,
+                                                                     int pps, Prep1IO io,
+                                                                     const uint2 *__restrict__ seg) {
+    prepare1_body<true>(base, reward, value, policy, beta, noise, bak, pps, io, seg);
+}
+
+// The per-tree seed table of mz_set_seed_segments, trees [c.first[0], c.first[c.n]) of it: tree t of
+// segment g gets {seeds[g], root_offsets[g] - first_tree[g]} (seed_value_seg).  Up to kSegChunk
+// segments per launch, in the argument block: no staging buffer, no copy.
+constexpr int kSegChunk = 32;
+struct SegChunk {
+    int n;
+    int first[kSegChunk + 1];
+    unsigned seed[kSegChunk];
+    unsigned off[kSegChunk];
+};
+__global__ __launch_bounds__(256) void k_set_segments(uint2 *__restrict__ tab, SegChunk c) {
+    const int t = c.first[0] + (int)(blockIdx.x * 256 + threadIdx.x);
+    if (t >= c.first[c.n]) return;
+    int g = 0;
+    while (g + 1 < c.n && t >= c.first[g + 1]) ++g;
+    tab[t] = make_uint2(c.seed[g], c.off[g] - (unsigned)c.first[g]);
 }
 
 // mz_create's device initialisation in one launch (instead of three copies and three memsets,
@@ -5856,6 +5911,11 @@ struct mz_batch {
     int tree_nc = -1;          // k_tree node class for 2 <= K <= 64 trees (-1: k_step)
     bool hbm = false;          // the pool's LDS image exceeds a CU's LDS: every step launch is k_hbm
     bool seed_ref = false;     // holds a reference on its device's seeding table (seed_table)
+    // per-segment seeds (mz_set_seed_segments): the per-tree table [B] -- an allocation of its own, made
+    // by the first call -- and the host's copy of the segments (empty: the handle's seed words)
+    uint2 *seg_tab = nullptr;
+    std::vector<int> seg_first, seg_off;
+    std::vector<unsigned> seg_seed;
     // device bytes by kind (mz_arena_info): pUCT tables, value entries, engine streams, node records
     size_t mem_tables = 0, mem_values = 0, mem_stream = 0, mem_nodes = 0;
     Params *prm = nullptr;     // device copy of {geo, dev} (in the arena)
@@ -6929,8 +6989,10 @@ int mz_create(int B, int N, int A, int K, int S, float delta_lb, uint32_t seed, 
     }
     if (N > 1) {  // k_prepare's dynamic LDS for the root's joint inputs (mz_prepare)
         const int jl = ((12 * b->NA + 15) & ~15) + 8 * b->NA + 4 * kWave * N;
-        if (jl > 48 * 1024)
+        if (jl > 48 * 1024) {
             (void)hipFuncSetAttribute((const void *)k_prepare, hipFuncAttributeMaxDynamicSharedMemorySize, jl);
+            (void)hipFuncSetAttribute((const void *)k_prepare_seg, hipFuncAttributeMaxDynamicSharedMemorySize, jl);
+        }
     }
     if (!b->hbm && g.lds > 64 * 1024) {
         if (N > 1) set_lds_limit<0, true>(g.lds);
@@ -6989,6 +7051,7 @@ int mz_destroy(mz_batch *b) {
     if (b->order_ev) (void)hipEventDestroy(b->order_ev);
     if (b->st_ev) (void)hipEventDestroy(b->st_ev);
     if (b->seed_ref) seed_table_release(b->device);
+    if (b->seg_tab) (void)hipFree(b->seg_tab);
     delete b;
     return MZ_OK;
 }
@@ -7031,6 +7094,7 @@ int mz_synchronize(mz_batch *b) {
 namespace {
 // the handle's prepare kernel (mz_create: k_prepare1 for K = 1 single-agent handles of A <= 64)
 void launch_prepare(mz_batch *b, const PrepArgs &a, size_t jl) {
+    const bool seg = !b->seg_first.empty();  // (mz_set_seed_segments: the kernels that read the per-tree table)
     if (b->prep1) {
         Prep1IO io = b->prep1_io;
         io.idx_x = a.idx_x;
@@ -7038,8 +7102,17 @@ void launch_prepare(mz_batch *b, const PrepArgs &a, size_t jl) {
         io.act = a.act;
         io.eps = a.eps;
         const int bak = b->B | (b->A << 24), pps = b->P | (b->PS << 16);
+        if (seg) {
+            hipLaunchKernelGGL(k_prepare1_seg, dim3(b->B), dim3(kPrep1Waves * kWave), 0, b->stream, (char *)b->dev.base,
+                               a.reward, a.value, a.policy, a.beta, a.noise, bak, pps, io, (const uint2 *)b->seg_tab);
+            return;
+        }
         hipLaunchKernelGGL(k_prepare1, dim3(b->B), dim3(kPrep1Waves * kWave), 0, b->stream, (char *)b->dev.base,
                            a.reward, a.value, a.policy, a.beta, a.noise, bak, pps, io);
+        return;
+    }
+    if (seg) {
+        hipLaunchKernelGGL(k_prepare_seg, dim3(b->B), dim3(256), jl, b->stream, b->prm, a, (const uint2 *)b->seg_tab);
         return;
     }
     hipLaunchKernelGGL(k_prepare, dim3(b->B), dim3(256), jl, b->stream, b->prm, a);
@@ -7306,6 +7379,58 @@ int mz_set_root_offset(mz_batch *b, int root_offset) {
 int mz_get_root_offset(mz_batch *b, int *root_offset) {
     if (!b || !root_offset) return fail(MZ_ERR_ARG, "mz_get_root_offset: null argument");
     *root_offset = b->root_offset;
+    return MZ_OK;
+}
+
+int mz_set_seed_segments(mz_batch *b, int n, const int32_t *first_tree, const uint32_t *seeds,
+                         const int32_t *root_offsets) {
+    if (!b) return fail(MZ_ERR_ARG, "null handle");
+    if (n < 0 || n > b->B) return fail(MZ_ERR_ARG, "seed segments: n must be in [0, root_num]");
+    if (n > 0 && (!first_tree || !seeds || !root_offsets)) return fail(MZ_ERR_ARG, "seed segments: null array");
+    for (int g = 0; g < n; ++g) {
+        const long long lo = first_tree[g], hi = g + 1 < n ? (long long)first_tree[g + 1] : (long long)b->B;
+        if (g == 0 && lo != 0) return fail(MZ_ERR_ARG, "seed segments: first_tree[0] must be 0");
+        if (lo >= hi) return fail(MZ_ERR_ARG, "seed segments: first_tree must be strictly increasing below root_num");
+        if (root_offsets[g] < 0) return fail(MZ_ERR_ARG, "seed segments: root_offset must be >= 0");
+        if ((long long)root_offsets[g] + (hi - lo) > 0x7fffffffll)
+            return fail(MZ_ERR_ARG, "seed segments: root_offset + the segment's trees > INT32_MAX");
+    }
+    OrderMark om{b};
+    int rc = ensure_device(b);
+    if (rc) return rc;
+    rc = flush_pending(b);
+    if (rc) return rc;
+    if (n > 0 && !b->seg_tab) HIP_TRY(hipMalloc((void **)&b->seg_tab, sizeof(uint2) * (size_t)b->B));
+    // (the trees and a ready packed readback still hold the last search: only the next prepare reads it)
+    for (int g0 = 0; g0 < n; g0 += kSegChunk) {
+        SegChunk c{};
+        c.n = std::min(kSegChunk, n - g0);
+        for (int i = 0; i < c.n; ++i) {
+            c.first[i] = first_tree[g0 + i];
+            c.seed[i] = seeds[g0 + i];
+            c.off[i] = (unsigned)root_offsets[g0 + i];
+        }
+        c.first[c.n] = g0 + c.n < n ? first_tree[g0 + c.n] : b->B;
+        const int trees = c.first[c.n] - c.first[0];
+        hipLaunchKernelGGL(k_set_segments, dim3((unsigned)((trees + 255) / 256)), dim3(256), 0, b->stream, b->seg_tab, c);
+        HIP_TRY(hipGetLastError());
+        b->dirty = true;
+    }
+    b->seg_first.assign(first_tree, first_tree + n);
+    b->seg_seed.assign(seeds, seeds + n);
+    b->seg_off.assign(root_offsets, root_offsets + n);
+    return MZ_OK;
+}
+
+int mz_get_seed_segments(mz_batch *b, int cap, int *n, int32_t *first_tree, uint32_t *seeds, int32_t *root_offsets) {
+    if (!b || !n || cap < 0) return fail(MZ_ERR_ARG, "mz_get_seed_segments: null argument");
+    if (cap > 0 && (!first_tree || !seeds || !root_offsets)) return fail(MZ_ERR_ARG, "mz_get_seed_segments: null array");
+    *n = (int)b->seg_first.size();
+    for (int g = 0; g < *n && g < cap; ++g) {
+        first_tree[g] = b->seg_first[g];
+        seeds[g] = b->seg_seed[g];
+        root_offsets[g] = b->seg_off[g];
+    }
     return MZ_OK;
 }
 

@@ -122,6 +122,7 @@ class Tree_batch:
         )
         check(lib, rc, "Tree_batch")
         self._root_offset = int(root_offset)
+        self._segmented = False  # set_seed_segments gave the handle per-segment seeds
         self._keep = []  # host buffers that must outlive an enqueued call
         self._stream_ptr = None
         # device backends follow torch's current stream on every call (oracle libraries are host-only)
@@ -313,6 +314,52 @@ class Tree_batch:
         n = C.c_int(0)
         check(self._lib, fn(self._h, C.byref(n)), "root_offset")
         return int(n.value)
+
+    def set_seed_segments(self, first_tree, seeds, root_offsets=None):
+        """From the next prepare on, tree t of segment g (first_tree[g] <= t < first_tree[g + 1]; the last
+        segment runs to root_num) is the tree of a fresh Tree_batch(..., seeds[g],
+        root_offset=root_offsets[g]) at row t - first_tree[g] (include/mzdriver.h mz_set_seed_segments;
+        product library only): several searches, each with its own tree seed, ride on one handle.  Empty
+        lists return the handle to its (seed, root_offset) words.  One small launch on the current
+        stream, like reseed; call it outside a graph capture."""
+        fn = getattr(self._lib, "mz_set_seed_segments", None)
+        if fn is None:
+            raise RuntimeError("set_seed_segments: this tree library has no mz_set_seed_segments "
+                               "(include/mzdriver.h, product library only)")
+        first = np.ascontiguousarray(np.asarray(first_tree, dtype=np.int64).reshape(-1))
+        sd = np.ascontiguousarray(np.asarray(seeds, dtype=np.int64).reshape(-1))
+        off = np.zeros_like(first) if root_offsets is None else \
+            np.ascontiguousarray(np.asarray(root_offsets, dtype=np.int64).reshape(-1))
+        if not (first.shape == sd.shape == off.shape):
+            raise ValueError("set_seed_segments: first_tree, seeds and root_offsets differ in length")
+        lim = 1 << 31
+        if first.size and (np.abs(first).max() >= lim or np.abs(off).max() >= lim):
+            raise ValueError("set_seed_segments: first_tree / root_offsets beyond int32")
+        first32, off32 = first.astype(np.int32), off.astype(np.int32)
+        sd32 = (sd & 0xFFFFFFFF).astype(np.uint32)
+        self._sync_stream()
+        check(self._lib, fn(self._h, int(first32.size), first32.ctypes.data_as(C.POINTER(C.c_int32)),
+                            sd32.ctypes.data_as(C.POINTER(C.c_uint32)), off32.ctypes.data_as(C.POINTER(C.c_int32))),
+              "set_seed_segments")
+        self._segmented = first32.size > 0
+
+    @property
+    def seed_segments(self):
+        """The handle's seed segments as (first_tree, seeds, root_offsets) lists, empty when it has none
+        (the library's host copy, mz_get_seed_segments: no device call)."""
+        fn = getattr(self._lib, "mz_get_seed_segments", None)
+        if fn is None:
+            return [], [], []
+        n = C.c_int(0)
+        check(self._lib, fn(self._h, 0, C.byref(n), None, None, None), "seed_segments")
+        first = np.zeros(max(n.value, 1), np.int32)
+        sd = np.zeros(max(n.value, 1), np.uint32)
+        off = np.zeros(max(n.value, 1), np.int32)
+        check(self._lib, fn(self._h, int(n.value), C.byref(n), first.ctypes.data_as(C.POINTER(C.c_int32)),
+                            sd.ctypes.data_as(C.POINTER(C.c_uint32)), off.ctypes.data_as(C.POINTER(C.c_int32))),
+              "seed_segments")
+        k = int(n.value)
+        return first[:k].tolist(), sd[:k].tolist(), off[:k].tolist()
 
     def state_changed(self):
         """Drop host-side readback caches after replaying a captured graph of this handle's calls."""

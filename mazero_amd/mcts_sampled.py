@@ -106,6 +106,15 @@ class DeviceSearchOutput(NamedTuple):
                             self.marginal_priors.cpu().numpy(), *[lists(f) for f in _SAMPLED_FIELDS])
 
 
+def slice_search_output(out: DeviceSearchOutput, lo: int, hi: int) -> DeviceSearchOutput:
+    """Rows [lo, hi) of a DeviceSearchOutput as views: one entry of SampledMCTS.batch_search_many_device
+    (its row bounds).  The per-root lists stay padded to the whole output's widest root; `to_host()` gives
+    the entry's SearchOutput.  The slice keeps no tree: the consumers that size their launches by the
+    handle's active roots take the whole output."""
+    return DeviceSearchOutput(out.value[lo:hi], out.marginal_visit_count[lo:hi], out.marginal_priors[lo:hi],
+                              out.degrees[lo:hi], {k: v[lo:hi] for k, v in out.sampled.items()}, None)
+
+
 def _np(x):
     if isinstance(x, torch.Tensor):
         return x.detach().cpu().numpy()
@@ -602,6 +611,8 @@ def _support_bounds(support) -> Tuple[int, int]:
 _DEVICE_OFFSET = "device_root_offset"
 # the place of the current agent in the key of a joint search's loop (no agent index is negative)
 _JOINT_AGENT = -1
+# the last element of the key of a merged search's loop (batch_search_many: per-segment tree seeds)
+_SEGMENTED = "seed_segments"
 
 
 def skip_search_draws(config, np_random, total: int, num_agents: int = 1) -> None:
@@ -756,10 +767,11 @@ class SampledMCTS:
         self.device_root = device_root
 
     # ---------------------------------------------------------------------------------------
-    def root_inputs(self, network_output, current_agent_idx, legal_actions_lst, add_noise, sampled_tau):
+    def root_inputs(self, network_output, current_agent_idx, legal_actions_lst, add_noise, sampled_tau, draw=None):
         """Root preprocessing, mcts_sampled.py:51-106, in numpy on the host (it draws from
         np_random).  Returns the prepare() arguments and the tree seed.  `current_agent_idx` None: the
-        joint search's (batch_search_joint), every agent's row, [B, N, A] arrays."""
+        joint search's (batch_search_joint), every agent's row, [B, N, A] arrays.  `draw`: the (noise,
+        seed) pair of an earlier draw_search(B) instead of fresh draws."""
         cfg = self.config
         alpha, eps = cfg.root_dirichlet_alpha, cfg.root_exploration_fraction
         A = cfg.action_space_size
@@ -772,7 +784,8 @@ class SampledMCTS:
         probs = np.exp(logits - np.max(logits, axis=-1, keepdims=True))
         probs = probs / np.sum(probs, axis=-1, keepdims=True)
         # Dirichlet noise is always drawn, then disabled for evaluation, :68-70
-        noises = self.draw_rows(lambda n: self.np_random.dirichlet([alpha] * A, (n, R) if joint else n), B)
+        noises = self.draw_rows(lambda n: self.np_random.dirichlet([alpha] * A, (n, R) if joint else n), B) \
+            if draw is None else np.asarray(draw[0])
         noises = noises.astype(np.float32).reshape(B, R, A)
         if not add_noise:
             eps = 0.0
@@ -785,7 +798,7 @@ class SampledMCTS:
             noises *= mask
             noises += mask * 1e-4
             noises = noises / np.sum(noises, axis=-1, keepdims=True)
-        seed = self.np_random.choice(256)  # drawn after the noise, :89
+        seed = self.np_random.choice(256) if draw is None else draw[1]  # drawn after the noise, :89
         beta = probs * (1 - eps) + noises * eps  # :93-100
         beta = beta ** (1 / sampled_tau)
         if mask is not None:
@@ -796,13 +809,14 @@ class SampledMCTS:
         return (rewards, values, probs.astype(np.float32), beta.astype(np.float32), eps,
                 noises.astype(np.float32, copy=False)), seed
 
-    def root_raw(self, network_output, current_agent_idx, legal_actions_lst, add_noise):
+    def root_raw(self, network_output, current_agent_idx, legal_actions_lst, add_noise, draw=None):
         """The raw root inputs of the device root preprocessing (mz_root_glue): the Dirichlet draws
         (np_random, then the tree seed, in the reference's order, mcts_sampled.py:68,89) and the
         arrays to upload, or None when the device path does not cover the inputs' dtypes (the host
         path, root_inputs, takes them).  Returns (arrays, (logits dtype code, has legal), eps, seed).
         `current_agent_idx` None: the joint search's (batch_search_joint), every agent's columns and one
-        Dirichlet row per (root, agent), for mz_root_glue_joint."""
+        Dirichlet row per (root, agent), for mz_root_glue_joint.  `draw`: the (noise, seed) pair of an
+        earlier draw_search(B) instead of fresh draws."""
         cfg = self.config
         A = cfg.action_space_size
         B = network_output.hidden_state.shape[0]
@@ -830,11 +844,14 @@ class SampledMCTS:
                 return None
             legal = legal.astype(np.int32)
         alpha, eps = cfg.root_dirichlet_alpha, cfg.root_exploration_fraction
-        noise = self.draw_rows(lambda n: self.np_random.dirichlet([alpha] * A, (n, R) if joint else n),
-                               B).astype(np.float32)
+        noise = self.draw_rows(lambda n: self.np_random.dirichlet([alpha] * A, (n, R) if joint else n), B) \
+            if draw is None else np.asarray(draw[0])
+        if noise.shape[0] != B:
+            raise ValueError(f"draws for {noise.shape[0]} roots, batch of {B}")
+        noise = noise.astype(np.float32)
         if not add_noise:
             eps = 0.0
-        seed = self.np_random.choice(256)  # drawn after the noise, :89
+        seed = self.np_random.choice(256) if draw is None else draw[1]  # drawn after the noise, :89
         arrays = dict(rewards=_np(network_output.reward).reshape(B).astype(np.float32),
                       values=_np(network_output.value).reshape(B).astype(np.float32), noise=noise, logits=logits)
         if legal is not None:
@@ -851,6 +868,16 @@ class SampledMCTS:
             raise ValueError(f"batch of {B} roots but the root shard is [{lo}, {hi})")
         return draw(total)[lo:hi]
 
+    def draw_search(self, B: int):
+        """What one per-agent search of B roots draws from `np_random` before it launches anything --
+        the Dirichlet rows, then the tree seed (mcts_sampled.py:68,89) -- as a (noise, seed) pair for
+        batch_search_many's `draws=`: a caller draws in the reference's order for searches it runs later,
+        in another grouping."""
+        cfg = self.config
+        noise = self.draw_rows(lambda n: self.np_random.dirichlet([cfg.root_dirichlet_alpha] * cfg.action_space_size,
+                                                                  n), int(B))
+        return noise, self.np_random.choice(256)
+
     def skip_search(self, num_agents: int = 1) -> None:
         """Consume from `np_random` exactly what one search consumes -- the Dirichlet rows of the whole
         batch, then the tree seed (mcts_sampled.py:68,89) -- and launch nothing: the search of an empty
@@ -864,9 +891,11 @@ class SampledMCTS:
         """One double per root in root order, as B np_random.choice(n, p) calls draw them."""
         return np.asarray(self.draw_rows(lambda n: self.np_random.random(n), B), dtype=np.float64)
 
-    def _tree(self, B, seed, device, agent_num: int = 1):
+    def _tree(self, B, seed, device, agent_num: int = 1, segments=None):
         """The cached handle of this geometry, reseeded.  `agent_num` > 1: joint-action trees
-        (batch_search_joint); what the handle refuses (A > 64, K > 64, N * A > 4096) raises here."""
+        (batch_search_joint); what the handle refuses (A > 64, K > 64, N * A > 4096) raises here.
+        `segments` = (first_tree, seeds, root_offsets): the trees of several searches
+        (Tree_batch.set_seed_segments)."""
         cfg = self.config
         # (pb_c_base, pb_c_init) select the handle's pUCT tables, which a graph replay does not
         # rewrite: a handle serves one pair only
@@ -892,6 +921,12 @@ class SampledMCTS:
             # (in the stream order of the reseed: the next prepare, eager or replayed, reads both words)
             if self.device_root_offset and tb.root_offset != self._root_offset():
                 tb.set_root_offset(self._root_offset())
+            # per-segment seeds (batch_search_many), in the same stream order; a plain search on a handle
+            # that a merged search used last returns it to its (seed, root_offset) words
+            if segments is not None:
+                tb.set_seed_segments(*segments)
+            elif tb._segmented:
+                tb.set_seed_segments([], [])
             return tb
 
     def _root_offset(self) -> int:
@@ -914,9 +949,6 @@ class SampledMCTS:
         """The search with device-resident outputs (DeviceSearchOutput), for on-device consumers."""
         if sampled_actions_res is not None:
             raise NotImplementedError  # as the reference, mcts_sampled.py:108-109
-        cfg = self.config
-        c2, c1, disc = cfg.pb_c_base, cfg.pb_c_init, cfg.discount
-        A, K, S = cfg.action_space_size, cfg.sampled_action_times, cfg.num_simulations
         N, cur = int(true_num_agents), int(current_agent_idx)
         # a joint search (batch_search_joint_device): no current agent; None selects every agent's root
         # inputs, and _JOINT_AGENT stands in the loop's key where a per-agent loop has its agent
@@ -940,13 +972,27 @@ class SampledMCTS:
             (rr, rv, rp, rb, eps, rn), seed = self.root_inputs(network_output, root_agent, legal_actions_lst,
                                                                add_noise, sampled_tau)
             root_arrays, root_mode = (rr, rv, rp, rb, rn), None
+        return self._search(model, hidden, root_arrays, root_mode, eps, seed, factor, N, cur, sampled_tau, Bc,
+                            _joint, _host_readback)
+
+    def _search(self, model, hidden, root_arrays, root_mode, eps, seed, factor, N, cur, sampled_tau, Bc,
+                _joint=False, _host_readback=False, segments=None):
+        """The search behind the root draws: the handle and the loop of Bc roots, the load, the run or the
+        replay, the readback.  `segments`: a merged search's (batch_search_many_device), which returns the
+        whole handle's rows."""
+        cfg = self.config
+        disc = cfg.discount
+        A, S = cfg.action_space_size, cfg.num_simulations
+        dev = hidden.device
+        B = hidden.shape[0]
         with torch.cuda.device(dev):
-            tb = self._tree(Bc, seed, dev, N if _joint else 1)
-            # the discount is a kernel argument of the recorded launches
+            tb = self._tree(Bc, seed, dev, N if _joint else 1, segments)
+            # the discount is a kernel argument of the recorded launches; a segmented loop records the
+            # prepare kernel that reads the per-tree seed table
             key = (threading.get_ident(), id(tb), id(model), N, _JOINT_AGENT if _joint else cur, float(eps),
                    float(sampled_tau), float(disc),
                    (Bc,) + tuple(hidden.shape[1:]), hidden.dtype, root_mode, self.wide_actions, self.fused_transforms,
-                   self.wide_supports, self.later_action_cache)
+                   self.wide_supports, self.later_action_cache) + (() if segments is None else (_SEGMENTED,))
             with _LOCK:
                 for k in [k for k, v in _LOOPS.items() if v.model_ref() is None]:
                     del _LOOPS[k]  # loops (graph, pool) of models that no longer exist
@@ -1002,6 +1048,140 @@ class SampledMCTS:
             tb.get_roots_device(disc, values=value, marginal_visit_count=mv, marginal_priors=mp, degrees=deg,
                                 sampled=sampled)
             return DeviceSearchOutput(value, mv, mp, deg, sampled, tb)
+
+    # ---------------------------------------------------------------------------------------
+    def batch_search_many(self, model, network_outputs: list, current_agent_idx, factors: list,
+                          true_num_agents: int, legal_actions_lsts: list = None, device: torch.device = None,
+                          add_noise=False, sampled_tau=1.0, draws: list = None) -> List[SearchOutput]:
+        """Several independent searches of one agent as one search over the concatenated roots: entry g
+        of the result equals, field by field and bit by bit, what the g-th of the consecutive calls
+        `batch_search(model, network_outputs[g], current_agent_idx, factors[g], true_num_agents,
+        legal_actions_lsts[g], device, add_noise, sampled_tau)` returns, and `np_random` ends in the
+        state those calls leave: per entry and in order, dirichlet(B_g) then choice(256)
+        (mcts_sampled.py:68,89).  `draws`: per entry the (noise, seed) pair of an earlier
+        `draw_search(B_g)`, for searches whose draws the caller made in the reference's order before
+        grouping them otherwise; nothing is drawn here then.
+
+        One tree handle and one recorded loop of sum(B_g) roots -- or of `root_capacity` C >= sum(B_g),
+        padded as batch_search pads -- whose trees are seeded per segment (Tree_batch.set_seed_segments:
+        entry g's tree i is tree i of a fresh Tree_batch under entry g's seed).  The guarantee is
+        `root_capacity`'s: exact whenever row i of the model's outputs and of the transforms does not
+        depend on how many rows the batch has.  `fused_transforms`, `wide_supports`,
+        `later_action_cache`, `wide_actions` and `root_capacity` compose.  `current_agent_idx`,
+        `add_noise` and `sampled_tau` may be per-entry sequences; entries that differ in them or in their
+        dtypes, a `root_shard`, and sum(B_g) over the capacity raise ValueError before anything launches
+        (the joint search has no merged form: batch_search_joint)."""
+        whole, bounds = self.batch_search_many_device(model, network_outputs, current_agent_idx, factors,
+                                                      true_num_agents, legal_actions_lsts, device, add_noise,
+                                                      sampled_tau, draws, _host_readback=True)
+        return [SearchOutput(*[np.ascontiguousarray(f[lo:hi]) if isinstance(f, np.ndarray) else list(f[lo:hi])
+                               for f in whole]) for lo, hi in zip(bounds[:-1], bounds[1:])]
+
+    def batch_search_many_device(self, model, network_outputs: list, current_agent_idx, factors: list,
+                                 true_num_agents: int, legal_actions_lsts: list = None, device=None,
+                                 add_noise=False, sampled_tau=1.0, draws: list = None,
+                                 _host_readback: bool = False):
+        """batch_search_many with device-resident outputs: (the whole handle's DeviceSearchOutput, the row
+        bounds [0, B_0, B_0 + B_1, ...]); entry g's rows are [bounds[g], bounds[g + 1]) of every tensor
+        (`slice_search_output`).  The consumers that take their row count from the handle
+        (mazero_amd.consume) run over the whole output."""
+        G = len(network_outputs)
+        if G < 1:
+            raise ValueError("batch_search_many: no entries")
+
+        def same(x, what):  # a scalar for every entry, or one per entry, all equal
+            if isinstance(x, (list, tuple, np.ndarray)):
+                vals = list(x)
+                if len(vals) != G:
+                    raise ValueError(f"batch_search_many: {len(vals)} {what} values for {G} entries")
+                if any(v != vals[0] for v in vals[1:]):
+                    raise ValueError(f"batch_search_many: the entries differ in {what} ({vals}); searches of "
+                                     "different agents, noise settings or temperatures do not merge")
+                return vals[0]
+            return x
+
+        cur = int(same(current_agent_idx, "current_agent_idx"))
+        add_noise = bool(same(add_noise, "add_noise"))
+        sampled_tau = float(same(sampled_tau, "sampled_tau"))
+        N = int(true_num_agents)
+        if self.root_shard is not None:
+            raise ValueError(f"batch_search_many with root_shard={self.root_shard}: a rank's draws are sliced from "
+                             "the whole batch's; merged searches across root shards are not supported")
+        factors = [None] * G if factors is None else list(factors)
+        legal_actions_lsts = [None] * G if legal_actions_lsts is None else list(legal_actions_lsts)
+        if len(factors) != G or len(legal_actions_lsts) != G or (draws is not None and len(draws) != G):
+            raise ValueError(f"batch_search_many: factors, legal_actions_lsts and draws must hold {G} entries")
+        hiddens = [o.hidden_state for o in network_outputs]
+        for hd in hiddens:
+            if not (isinstance(hd, torch.Tensor) and hd.is_cuda):
+                raise ValueError("network_output.hidden_state must be a GPU tensor")
+            if hd.shape[0] < 1:
+                raise ValueError("batch_search_many: an entry of 0 roots")
+        sizes = [int(hd.shape[0]) for hd in hiddens]
+        total = sum(sizes)
+        Bc = total if self.root_capacity is None else self.root_capacity
+        if total > Bc:
+            raise ValueError(f"entries of {sizes} roots, {total} together, exceed root_capacity={Bc}")
+
+        def kind(o, legal):  # what has to agree for the entries' rows to share the loop's buffers
+            lg = o.policy_logits
+            if getattr(lg, "ndim", 0) != 3:
+                raise ValueError("batch_search_many takes per-agent searches ([B, num_agents, A] logits); the joint "
+                                 "search has no merged form")
+            return (str(lg.dtype).replace("torch.", ""), isinstance(lg, torch.Tensor), str(o.hidden_state.dtype),
+                    tuple(o.hidden_state.shape[1:]), o.hidden_state.device, legal is not None,
+                    None if legal is None else _np(legal).dtype.kind in "iub")
+
+        kinds = [kind(o, la) for o, la in zip(network_outputs, legal_actions_lsts)]
+        if any(k != kinds[0] for k in kinds[1:]):
+            raise ValueError(f"batch_search_many: the entries differ in dtype, device or legal-action form: {kinds}")
+        if cur > 0 and any(f is None for f in factors):
+            raise ValueError(f"batch_search_many: agent {cur} needs every entry's factor")
+
+        # the draws, entry after entry in the reference's order, then each entry's root inputs
+        parts, seeds, modes, epss = [], [], [], []
+        for g in range(G):
+            d = None if draws is None else draws[g]
+            raw = self.root_raw(network_outputs[g], cur, legal_actions_lsts[g], add_noise, draw=d) \
+                if self.device_root else None
+            if raw is not None:
+                arrays, mode, eps, seed = raw
+            else:
+                (rr, rv, rp, rb, eps, rn), seed = self.root_inputs(network_outputs[g], cur, legal_actions_lsts[g],
+                                                                   add_noise, sampled_tau, draw=d)
+                arrays, mode = (rr, rv, rp, rb, rn), None
+            parts.append(arrays)
+            seeds.append(int(seed))
+            modes.append(mode)
+            epss.append(eps)
+        if any(m != modes[0] for m in modes[1:]):
+            raise ValueError(f"batch_search_many: the entries take different root paths: {modes}")
+        root_mode, eps = modes[0], epss[0]
+
+        def cat(xs):
+            if all(isinstance(x, torch.Tensor) for x in xs):
+                return torch.cat([x.reshape(x.shape[0], -1) for x in xs], 0)
+            return np.concatenate([np.asarray(x).reshape(np.asarray(x).shape[0], -1) for x in xs], 0)
+
+        if root_mode is not None:
+            root_arrays = {k: cat([p[k] for p in parts]) for k in parts[0]}
+        else:
+            root_arrays = tuple(cat([p[i] for p in parts]) for i in range(5))
+        hidden = torch.cat(hiddens, 0)
+        dev = hidden.device
+        factor = None
+        if cur > 0:
+            factor = torch.cat([torch.as_tensor(np.ascontiguousarray(_np(f)[:, :cur]) if not isinstance(f, torch.Tensor)
+                                                else f[:, :cur]).to(device=dev, dtype=torch.int32) for f in factors], 0)
+        bounds = [0]
+        for b in sizes:
+            bounds.append(bounds[-1] + b)
+        # (the last segment runs to the handle's root count: under root_capacity the padding trees
+        # continue the last entry's batch, and nobody reads them)
+        segments = (bounds[:-1], seeds, [0] * G)
+        out = self._search(model, hidden, root_arrays, root_mode, eps, seeds[0], factor, N, cur, sampled_tau, Bc,
+                           False, _host_readback, segments=segments)
+        return out, bounds
 
     # ---------------------------------------------------------------------------------------
     def batch_search_joint(self, model, network_output, legal_actions_lst: np.ndarray = None,

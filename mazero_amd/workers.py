@@ -330,3 +330,31 @@ class ReanalyzeShard(_Shard):
             td_max=td_max, use_root_value=use_root_value, use_pred_value=not use_root_value,
             rows=(self.lo, self.hi), device=self.device)
         return dict(batch_rewards=_to_np(r), batch_values=_to_np(v), model_index=idx, lo=self.lo)
+
+    def batch_targets(self, value_obs, value_legal, policy_obs, policy_legal, policy_mask, *, rewards, pos, traj_len,
+                      td_steps, num_unroll_steps: int, discount: Optional[float] = None, td_max: Optional[int] = None
+                      ) -> dict:
+        """`value_targets(value_obs, value_legal, ...)` followed by `targets(policy_obs, policy_legal,
+        policy_mask)` with one search fewer: the value search and the agent-0 policy search run as one
+        merged search (consume.reanalyze_batch_targets, SampledMCTS.batch_search_many).  The result holds
+        both calls' entries, and `np_random` ends where the two calls leave it.  One weight sync and one
+        model index serve both.  A merged search draws each entry's own rows, so the rank must own the
+        whole batch (world == 1); across root shards it raises ValueError, and the two calls remain."""
+        if self.world != 1:
+            raise ValueError(f"batch_targets on rank {self.rank} of {self.world}: merged searches do not cross "
+                             "root shards (value_targets and targets do)")
+        if len(pos) * (int(num_unroll_steps) + 1) != self.total:
+            raise ValueError(f"{len(pos)} trajectories x {int(num_unroll_steps) + 1} rows != {self.total} roots")
+        idx = self._sync()
+        value_out = self._initial_inference(value_obs)
+        policy_out = self._initial_inference(policy_obs)
+        mcts = self.make_mcts(self.config, self.np_random, None)
+        from .consume import reanalyze_batch_targets
+
+        r, v, pol = reanalyze_batch_targets(
+            mcts, self.model, value_out, value_legal, policy_out, policy_legal, policy_mask, rewards=rewards, pos=pos,
+            traj_len=traj_len, td_steps=td_steps, discount=self.config.discount if discount is None else discount,
+            num_unroll_steps=num_unroll_steps, td_max=td_max, rows=(self.lo, self.hi), device=self.device)
+        out = {k: _to_np(x) for k, x in pol._asdict().items()}
+        out.update(batch_rewards=_to_np(r), batch_values=_to_np(v), model_index=idx, lo=self.lo)
+        return out
