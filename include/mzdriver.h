@@ -224,6 +224,47 @@ int mz_joint_action_cached(mz_batch *b, const int32_t *later_pool, int slots, co
                            int num_agents, int current_agent, const int32_t *factor, int factor_cols,
                            const int32_t *actions, int64_t *joint_out);
 
+/* The current agent per root (mcts_sampled.py:116-147,156-161 with a current_agent_idx of its own in
+ * every row): the _rows entry points take `row_agent`, device memory, int32 [B], in place of the scalar
+ * agent or column offset of the entry point they mirror, so that one launch -- and one recorded graph,
+ * which reads the table when it is replayed -- serves roots whose searches are of different agents
+ * (mazero_amd.mcts_sampled mixed_agents).  Row i of every output holds the bytes the mirrored entry point
+ * writes there for current_agent = row_agent[i].  A wave reads its root's entry as one scalar, so the row
+ * code runs in the wave-uniform control flow it has with a launch constant.  The launchers cannot see the
+ * table: the kernels clamp an entry outside [0, num_agents) to 0 or num_agents - 1, so no value indexes
+ * outside a logits row, a factor row or the later pool; a driver validates before it uploads.  Any
+ * action_space_size the handle has (1..255), the tiles of the _wide entry points.  Nothing is allocated
+ * or uploaded, so the calls can be captured in a graph.
+ *
+ * mz_policy_glue_rows: row i is mz_policy_glue(..., col_offset = row_agent[i] * A, ...) (mz_policy_glue_wide
+ * for A > 64).  logits [B, num_agents, A] of dtype `dtype`, row stride `row_stride` >= num_agents * A
+ * elements; probs_out, beta_out float32 [B, A].
+ *
+ * mz_joint_action_rows: row i is mz_joint_action with current_agent = row_agent[i].  factor: int32
+ * [B, factor_cols], of which row i reads its first row_agent[i] columns; factor_cols >= max(1,
+ * num_agents - 1) (NULL only with one agent).  pred_logits [B, num_agents, A], contiguous (NULL only with
+ * one agent); num_agents <= 64; joint_out int64 [B, num_agents].
+ *
+ * mz_policy_glue_later_rows: mz_policy_glue_later on a grid of (B, num_agents) workgroups, (B, num_agents
+ * - 1) for the argmax-only form (probs_out and beta_out both NULL).  Role 0 is the policy glue of agent
+ * row_agent[i]; role j >= 1 is np.argmax of agent row_agent[i] + j's logits into later_out[i, row_agent[i]
+ * + j], and returns at once when that agent is >= num_agents.  Columns <= row_agent[i] of row i of
+ * later_out (int32 [B, num_agents]) are not written.  later_out may be NULL with one agent.
+ *
+ * mz_joint_action_cached_rows: mz_joint_action_cached with current_agent = row_agent[i] in row i; factor
+ * and factor_cols as mz_joint_action_rows; later_pool, slots, idx_x as mz_joint_action_cached (NULL only
+ * with one agent). */
+int mz_policy_glue_rows(mz_batch *b, const void *logits, int dtype, int64_t row_stride, int num_agents,
+                        const int32_t *row_agent, double sampled_tau, float *probs_out, float *beta_out);
+int mz_joint_action_rows(mz_batch *b, const void *pred_logits, int dtype, int num_agents, const int32_t *row_agent,
+                         const int32_t *factor, int factor_cols, const int32_t *actions, int64_t *joint_out);
+int mz_policy_glue_later_rows(mz_batch *b, const void *logits, int dtype, int64_t row_stride, int num_agents,
+                              const int32_t *row_agent, double sampled_tau, float *probs_out, float *beta_out,
+                              int32_t *later_out);
+int mz_joint_action_cached_rows(mz_batch *b, const int32_t *later_pool, int slots, const int32_t *idx_x,
+                                int num_agents, const int32_t *row_agent, const int32_t *factor, int factor_cols,
+                                const int32_t *actions, int64_t *joint_out);
+
 /* The glue of a joint search (a handle of agent_num = N > 1, whose prepare and expansion take
  * [B, N, A] policy, beta and noise): every agent's row in one launch, one wave per (root, agent).
  * The kernel is that of mz_policy_glue / mz_root_glue with an agent per grid row, so for every agent k

@@ -133,6 +133,15 @@ DRIVER_SIGNATURES = {
     # num_agents, current_agent, factor, factor_cols, actions, joint_out)
     "mz_policy_glue_later": (_i, [_p, _p, _i, _i64, _i, _i, C.c_double, _p, _p, _p]),
     "mz_joint_action_cached": (_i, [_p, _p, _i, _p, _i, _i, _p, _i, _p, _p]),
+    # the current agent per root: `row_agent` (device int32 [B]) in place of the scalar agent / column offset:
+    # (handle, logits, dtype, row_stride, num_agents, row_agent, sampled_tau, probs_out, beta_out),
+    # (handle, pred_logits, dtype, num_agents, row_agent, factor, factor_cols, actions, joint_out),
+    # (handle, logits, dtype, row_stride, num_agents, row_agent, sampled_tau, probs_out, beta_out, later_out),
+    # (handle, later_pool, slots, idx_x, num_agents, row_agent, factor, factor_cols, actions, joint_out)
+    "mz_policy_glue_rows": (_i, [_p, _p, _i, _i64, _i, _p, C.c_double, _p, _p]),
+    "mz_joint_action_rows": (_i, [_p, _p, _i, _i, _p, _p, _i, _p, _p]),
+    "mz_policy_glue_later_rows": (_i, [_p, _p, _i, _i64, _i, _p, C.c_double, _p, _p, _p]),
+    "mz_joint_action_cached_rows": (_i, [_p, _p, _i, _p, _i, _p, _p, _i, _p, _p]),
     # the glue of a joint search, every agent in one launch: (handle, logits, dtype, row_stride, num_agents,
     # sampled_tau, probs_out, beta_out) and (handle, logits, dtype, row_stride, num_agents, legal,
     # legal_stride, noises, noise_eps, sampled_tau, probs_out, beta_out, noises_out)

@@ -323,6 +323,85 @@ def reanalyze_policy_targets(mcts, model, network_output, legal_actions_lst, pol
                            torch.ones(B, 1, dtype=torch.float32, device=dev), masks, value0, value0, pv)
 
 
+def agent_wavefront(G: int, N: int) -> List[List[Tuple[int, int]]]:
+    """The order in which the N dependent agent searches of G independent batches can run merged: tick t
+    holds every (batch g, agent k) with k = t - g and 0 <= k < N, in ascending g.  Agent k of a batch needs
+    the actions of that batch's agents before k (reanalyze_worker.py:278-317) and nothing of another
+    batch, so the N x G grid has dependencies along one axis only: (g, k - 1) lies one tick before (g, k),
+    no tick holds a batch twice, and G + N - 1 ticks replace G * N searches."""
+    G, N = int(G), int(N)
+    if G < 1 or N < 1:
+        raise ValueError(f"agent_wavefront: {G} batches of {N} agents")
+    return [[(g, t - g) for g in range(G) if 0 <= t - g < N] for t in range(G + N - 1)]
+
+
+def reanalyze_policy_targets_many(mcts, model, network_outputs: list, legal_actions_lsts: list, policy_masks: list,
+                                  device=None) -> List[ReanalyzePolicy]:
+    """`reanalyze_policy_targets` of G batches, their agent searches run as a wavefront (agent_wavefront):
+    one merged search per tick over entries of different agents (SampledMCTS.batch_search_many_device on a
+    `mixed_agents` driver) and one mz_marginal_policy launch over its rows.  Entry g equals, all seven
+    fields and bit for bit, the g-th of the consecutive calls `reanalyze_policy_targets(mcts, model,
+    network_outputs[g], legal_actions_lsts[g], policy_masks[g], device)` under batch_search_many's
+    condition, and `np_random` ends in the state those calls leave: every search's draws are made first,
+    in the reference's order (batch 0's agents 0 .. N - 1, then batch 1's), and handed to the ticks.
+    Requires `mixed_agents=True` and num_simulations >= 1; a `root_shard` driver is refused; a
+    `root_capacity` must hold the largest tick.  All refusals come before anything is drawn."""
+    if mcts.config.num_simulations < 1:
+        raise ValueError("reanalyze_policy_targets_many needs num_simulations >= 1")
+    if not getattr(mcts, "mixed_agents", False):
+        raise ValueError("reanalyze_policy_targets_many needs a SampledMCTS with mixed_agents=True (a tick "
+                         "merges searches of different agents)")
+    if mcts.root_shard is not None:
+        raise ValueError(f"reanalyze_policy_targets_many with root_shard={mcts.root_shard}: merged searches across "
+                         "root shards are not supported")
+    G = len(network_outputs)
+    if G < 1 or len(legal_actions_lsts) != G or len(policy_masks) != G:
+        raise ValueError(f"reanalyze_policy_targets_many: {G} batches, {len(legal_actions_lsts)} legal-action "
+                         f"arrays and {len(policy_masks)} masks")
+    legal_np = [np.asarray(la) for la in legal_actions_lsts]
+    N = legal_np[0].shape[1]
+    sizes = [int(o.hidden_state.shape[0]) for o in network_outputs]
+    if any(la.ndim != 3 or la.shape[:2] != (b, N) for la, b in zip(legal_np, sizes)):
+        raise ValueError(f"reanalyze_policy_targets_many: legal actions of shapes {[la.shape for la in legal_np]} "
+                         f"for batches of {sizes} roots and {N} agents")
+    ticks = agent_wavefront(G, N)
+    largest = max(sum(sizes[g] for g, _ in tick) for tick in ticks)
+    if mcts.root_capacity is not None and largest > mcts.root_capacity:
+        raise ValueError(f"the largest tick holds {largest} roots, more than root_capacity={mcts.root_capacity}")
+    dev = network_outputs[0].hidden_state.device
+    draws = [[mcts.draw_search(b) for _ in range(N)] for b in sizes]  # the reference's order
+    legal = [_dev_i32(la, dev) for la in legal_np]
+    current = [torch.zeros(b, N, dtype=torch.int32, device=dev) for b in sizes]
+    prob = [torch.ones(b, dtype=torch.float64, device=dev) for b in sizes]
+    value0 = [None] * G
+    for tick in ticks:
+        whole, bounds = mcts.batch_search_many_device(
+            model, [network_outputs[g] for g, _ in tick], [k for _, k in tick],
+            [current[g][:, :k] if k > 0 else None for g, k in tick], N, [legal_np[g] for g, _ in tick], device,
+            add_noise=True, sampled_tau=1.0, draws=[draws[g][k] for g, k in tick])
+        # one launch over the merged rows: each row's legal actions are its own agent's, its running
+        # product its batch's (rows are independent: an entry's rows get what a launch over them alone writes)
+        legal_rows = torch.cat([legal[g][:, k, :] for g, k in tick], 0)
+        prob_rows = torch.cat([prob[g] for g, _ in tick], 0)
+        a = torch.empty(bounds[-1], dtype=torch.int32, device=dev)
+        with torch.cuda.device(dev):
+            marginal_policy(whole, MZ_MARGINAL_ARGMAX, a, prob_rows, legal=legal_rows)
+        for (g, k), lo, hi in zip(tick, bounds[:-1], bounds[1:]):
+            current[g][:, k] = a[lo:hi]
+            prob[g] = prob_rows[lo:hi]
+            if k == 0:
+                value0[g] = whole.value[lo:hi].reshape(sizes[g], 1)
+    res = []
+    for g, b in enumerate(sizes):
+        masks = torch.as_tensor(np.asarray(policy_masks[g]).reshape(b, 1).astype(np.bool_)).to(dev)
+        pv = torch.as_tensor(network_outputs[g].value).to(dev)
+        if pv.ndim == 1:
+            pv = pv.reshape(b, 1)
+        res.append(ReanalyzePolicy(current[g].reshape(b, 1, N), prob[g].to(torch.float32).reshape(b, 1),
+                                   torch.ones(b, 1, dtype=torch.float32, device=dev), masks, value0[g], value0[g], pv))
+    return res
+
+
 class GameReanalysis(NamedTuple):
     """What make_renalyze_update computes for the T = len(game) steps of one game
     (reanalyze_worker.py:515-596, :604-607), as device tensors."""

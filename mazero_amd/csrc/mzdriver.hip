@@ -379,6 +379,30 @@ __global__ __launch_bounds__(kWave) void k_policy_glue(const void *logits, long 
                             beta, hexp, blockIdx.x, (long long)blockIdx.x * R + blockIdx.y, threadIdx.x, lds);
 }
 
+// The current agent as per-row device state (the _rows entry points: rows of different agents in one
+// launch).  Every lane reads the one word row_agent[t] and the value is made a scalar, so whatever
+// depends on it -- the later agents' loop, the role test -- branches on SGPRs and the row bodies' ballots,
+// wave_max and DPP butterflies stay in wave-uniform control flow, as with the launch constant.  A value
+// outside [0, N) is clamped: no table indexes outside a logits row, a factor row or the later pool.
+__device__ __forceinline__ int row_agent_of(const int *row_agent, int t, int N) {
+    const int cur = __builtin_amdgcn_readfirstlane(row_agent[t]);
+    return cur < 0 ? 0 : cur >= N ? N - 1 : cur;
+}
+
+// k_policy_glue for root blockIdx.x's own agent (grid (B)): the table's pointer stands where col_off
+// stood and N where R stood, so the argument sequence and its preloaded part are k_policy_glue's.
+template <bool F16, int T>
+__global__ __launch_bounds__(kWave) void k_policy_glue_rows(const void *logits, long long row_stride,
+                                                            const int *row_agent, unsigned plan, int N, int use_pow,
+                                                            float tau_inv, float *probs, float *beta,
+                                                            const unsigned short *hexp) {
+    const int A = plan_len<T>(plan);
+    __shared__ float lds[kWave * T];
+    const int cur = row_agent_of(row_agent, blockIdx.x, N);
+    policy_glue_row<F16, T>(logits, row_stride, (long long)cur * A, A, plan, use_pow, tau_inv, probs, beta, hexp,
+                            blockIdx.x, blockIdx.x, threadIdx.x, lds);
+}
+
 // `x - m` of the root's softmax, m the row's maximum.  When m is a NaN numpy's result is a NaN operand
 // as it stands (x's own where x is one), sign included; the GPU's subtraction negates its second
 // operand first, a NaN's sign with it, so that case is picked by hand.
@@ -464,10 +488,11 @@ __global__ __launch_bounds__(kWave) void k_root_glue(const void *logits, long lo
 }
 
 // mcts_sampled.py:116-147 for root blockIdx.x: previous agents from `factor`, the current agent
-// from the selection, the following agents by numpy argmax of the leaf policy logits.
+// from the selection, the following agents by numpy argmax of the leaf policy logits.  `cur` is
+// wave-uniform (np_argmax_row's ballots): the launch's agent, or the root's own (k_joint_action_rows).
 template <bool F16, int T>
-__global__ __launch_bounds__(kWave) void k_joint_action(const void *pred, int N, int A, int cur, const int *factor,
-                                                        int fcols, const int *actions, long long *joint) {
+__device__ __forceinline__ void joint_action_row(const void *pred, int N, int A, int cur, const int *factor, int fcols,
+                                                 const int *actions, long long *joint) {
     const int t = blockIdx.x;
     const int l = threadIdx.x;
     if (l < N && l <= cur) joint[(long long)t * N + l] = (l < cur) ? (long long)factor[(long long)t * fcols + l]
@@ -476,6 +501,19 @@ __global__ __launch_bounds__(kWave) void k_joint_action(const void *pred, int N,
         const int idx = np_argmax_row<F16, T>(pred, ((long long)t * N + k) * A, A, l);
         if (l == 0) joint[(long long)t * N + k] = idx;
     }
+}
+
+template <bool F16, int T>
+__global__ __launch_bounds__(kWave) void k_joint_action(const void *pred, int N, int A, int cur, const int *factor,
+                                                        int fcols, const int *actions, long long *joint) {
+    joint_action_row<F16, T>(pred, N, A, cur, factor, fcols, actions, joint);
+}
+
+template <bool F16, int T>
+__global__ __launch_bounds__(kWave) void k_joint_action_rows(const void *pred, int N, int A, const int *row_agent,
+                                                             const int *factor, int fcols, const int *actions,
+                                                             long long *joint) {
+    joint_action_row<F16, T>(pred, N, A, row_agent_of(row_agent, blockIdx.x, N), factor, fcols, actions, joint);
 }
 
 // mz_policy_glue_later: one wave per (root, role), grid (B, roles).  Role 0 is the policy glue of the
@@ -503,15 +541,38 @@ __global__ __launch_bounds__(kWave) void k_policy_glue_later(const void *logits,
     if (l == 0) later[(long long)t * N + k] = idx;
 }
 
+// k_policy_glue_later with root t's own agent, grid (B, glue + N - 1): every root gets the roles of
+// agent 0, and the workgroups of a role past the root's last agent return at once.
+template <bool F16, int T>
+__global__ __launch_bounds__(kWave) void k_policy_glue_later_rows(const void *logits, long long row_stride,
+                                                                  const int *row_agent, unsigned plan, int N, int glue,
+                                                                  int use_pow, float tau_inv, float *probs,
+                                                                  float *beta, int *later,
+                                                                  const unsigned short *hexp) {
+    const int A = plan_len<T>(plan);
+    __shared__ float lds[kWave * T];
+    const int t = blockIdx.x;
+    const int l = threadIdx.x;
+    const int cur = row_agent_of(row_agent, t, N);
+    const int j = (int)blockIdx.y + 1 - glue;
+    if (j == 0) {
+        policy_glue_row<F16, T>(logits, row_stride, (long long)cur * A, A, plan, use_pow, tau_inv, probs, beta, hexp, t,
+                                t, l, lds);
+        return;
+    }
+    const int k = cur + j;
+    if (k >= N) return;  // (the workgroup's: cur and j are scalars)
+    const int idx = np_argmax_row<F16, T>(logits, (long long)t * row_stride + (long long)k * A, A, l);
+    if (l == 0) later[(long long)t * N + k] = idx;
+}
+
 // mz_joint_action_cached: one thread per (root i, agent k); the later agents' actions are those the
 // node selected for root i (its hidden_state_index_x, idx_x[i]) got from mz_policy_glue_later.
 constexpr int kCachedLanes = 256;
-__global__ __launch_bounds__(kCachedLanes) void k_joint_action_cached(const int *pool, int slots, const int *idx_x,
-                                                                      int B, int N, int cur, const int *factor,
-                                                                      int fcols, const int *actions,
-                                                                      long long *joint) {
-    const long long e = (long long)blockIdx.x * kCachedLanes + threadIdx.x;
-    if (e >= (long long)B * N) return;
+// element e = (root i, agent k) of the joint action; cur is root i's agent
+__device__ __forceinline__ void joint_action_cached_elem(const int *pool, int slots, const int *idx_x, int B, int N,
+                                                         int cur, const int *factor, int fcols, const int *actions,
+                                                         long long *joint, long long e) {
     const int i = (int)(e / N), k = (int)(e % N);
     long long v;
     if (k < cur) {
@@ -524,6 +585,28 @@ __global__ __launch_bounds__(kCachedLanes) void k_joint_action_cached(const int 
         v = pool[((long long)s * B + i) * N + k];
     }
     joint[e] = v;
+}
+
+__global__ __launch_bounds__(kCachedLanes) void k_joint_action_cached(const int *pool, int slots, const int *idx_x,
+                                                                      int B, int N, int cur, const int *factor,
+                                                                      int fcols, const int *actions,
+                                                                      long long *joint) {
+    const long long e = (long long)blockIdx.x * kCachedLanes + threadIdx.x;
+    if (e >= (long long)B * N) return;
+    joint_action_cached_elem(pool, slots, idx_x, B, N, cur, factor, fcols, actions, joint, e);
+}
+
+// k_joint_action_cached with root i's own agent, clamped to [0, N - 1] as the slot is (a lane's own
+// value: nothing here is a wave operation)
+__global__ __launch_bounds__(kCachedLanes) void k_joint_action_cached_rows(const int *pool, int slots, const int *idx_x,
+                                                                           int B, int N, const int *row_agent,
+                                                                           const int *factor, int fcols,
+                                                                           const int *actions, long long *joint) {
+    const long long e = (long long)blockIdx.x * kCachedLanes + threadIdx.x;
+    if (e >= (long long)B * N) return;
+    int cur = row_agent[e / N];
+    cur = cur < 0 ? 0 : cur >= N ? N - 1 : cur;
+    joint_action_cached_elem(pool, slots, idx_x, B, N, cur, factor, fcols, actions, joint, e);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1010,6 +1093,104 @@ int mz_joint_action_cached(mz_batch *b, const int32_t *later_pool, int slots, co
     hipLaunchKernelGGL(k_joint_action_cached, dim3((unsigned)((n + kCachedLanes - 1) / kCachedLanes)),
                        dim3(kCachedLanes), 0, g.stream, (const int *)later_pool, slots, (const int *)idx_x, g.B,
                        num_agents, current_agent, (const int *)factor, factor_cols, (const int *)actions,
+                       (long long *)joint_out);
+    return glue_end(g);
+}
+
+// The _rows entry points: the current agent from a device table, one entry per root.  The launchers
+// cannot see the table (the kernels clamp what it holds); what they check is what every agent needs.
+static int rows_agents(const Glue &g, int num_agents, int max_agents, const int32_t *row_agent) {
+    if (num_agents < 1 || num_agents > max_agents) return glue_fail(MZ_ERR_ARG, g.fn, "bad agent count");
+    if (!row_agent) return glue_fail(MZ_ERR_ARG, g.fn, "null row_agent");
+    return MZ_OK;
+}
+
+// factor [B, factor_cols]: a row of agent N - 1 reads N - 1 columns (none with one agent)
+static int rows_factor(const Glue &g, int num_agents, const int32_t *factor, int factor_cols) {
+    if (factor_cols < (num_agents > 2 ? num_agents - 1 : 1))
+        return glue_fail(MZ_ERR_ARG, g.fn, "factor_cols < max(1, num_agents - 1)");
+    if (num_agents > 1 && !factor) return glue_fail(MZ_ERR_ARG, g.fn, "factor must hold the previous agents' actions");
+    return MZ_OK;
+}
+
+int mz_policy_glue_rows(mz_batch *b, const void *logits, int dtype, int64_t row_stride, int num_agents,
+                        const int32_t *row_agent, double sampled_tau, float *probs_out, float *beta_out) {
+    const char *fn = "mz_policy_glue_rows";
+    Glue g;
+    if (int rc = glue_begin(&g, fn, b, true)) return rc;
+    if (int rc = rows_agents(g, num_agents, kMaxGridRows, row_agent)) return rc;
+    if (!logits || !probs_out || !beta_out) return glue_fail(MZ_ERR_ARG, fn, "null buffer");
+    if (int rc = glue_dtype(g, dtype)) return rc;
+    if (row_stride < (int64_t)num_agents * g.A)
+        return glue_fail(MZ_ERR_ARG, fn, "logits row does not hold every agent's actions");
+    if (int rc = glue_tau(&g, sampled_tau, dtype == MZ_DT_F16)) return rc;  // as mz_policy_glue
+    glue_dispatch(dtype, g.A, [&](auto f16, auto tiles) {
+        hipLaunchKernelGGL((k_policy_glue_rows<decltype(f16)::value, decltype(tiles)::value>), dim3(g.B), dim3(kWave),
+                           0, g.stream, logits, (long long)row_stride, (const int *)row_agent, g.plan, num_agents,
+                           g.use_pow, g.tau_inv, probs_out, beta_out, g.hexp);
+    });
+    return glue_end(g);
+}
+
+int mz_joint_action_rows(mz_batch *b, const void *pred_logits, int dtype, int num_agents, const int32_t *row_agent,
+                         const int32_t *factor, int factor_cols, const int32_t *actions, int64_t *joint_out) {
+    const char *fn = "mz_joint_action_rows";
+    Glue g;
+    if (int rc = glue_begin(&g, fn, b, true)) return rc;
+    if (int rc = rows_agents(g, num_agents, kWave, row_agent)) return rc;  // (a lane per earlier agent)
+    if (!actions || !joint_out) return glue_fail(MZ_ERR_ARG, fn, "null buffer");
+    if (int rc = rows_factor(g, num_agents, factor, factor_cols)) return rc;
+    if (num_agents > 1 && !pred_logits)
+        return glue_fail(MZ_ERR_ARG, fn, "leaf policy logits required for later agents");
+    if (int rc = glue_dtype(g, dtype)) return rc;
+    glue_dispatch(dtype, g.A, [&](auto f16, auto tiles) {
+        hipLaunchKernelGGL((k_joint_action_rows<decltype(f16)::value, decltype(tiles)::value>), dim3(g.B), dim3(kWave),
+                           0, g.stream, pred_logits, num_agents, g.A, (const int *)row_agent, (const int *)factor,
+                           factor_cols, (const int *)actions, (long long *)joint_out);
+    });
+    return glue_end(g);
+}
+
+int mz_policy_glue_later_rows(mz_batch *b, const void *logits, int dtype, int64_t row_stride, int num_agents,
+                              const int32_t *row_agent, double sampled_tau, float *probs_out, float *beta_out,
+                              int32_t *later_out) {
+    const char *fn = "mz_policy_glue_later_rows";
+    Glue g;
+    if (int rc = glue_begin(&g, fn, b, true)) return rc;
+    if (int rc = rows_agents(g, num_agents, kMaxGridRows, row_agent)) return rc;
+    if (!logits) return glue_fail(MZ_ERR_ARG, fn, "null buffer");
+    if (!probs_out != !beta_out) return glue_fail(MZ_ERR_ARG, fn, "probs_out and beta_out go together");
+    const int glue = probs_out ? 1 : 0, later = num_agents - 1;  // (a row of agent 0 has them all)
+    if (later > 0 && !later_out) return glue_fail(MZ_ERR_ARG, fn, "later_out required for later agents");
+    if (glue + later == 0) return glue_fail(MZ_ERR_ARG, fn, "no output asked for");
+    if (int rc = glue_dtype(g, dtype)) return rc;
+    if (row_stride < (int64_t)num_agents * g.A)
+        return glue_fail(MZ_ERR_ARG, fn, "logits row does not hold every agent's actions");
+    if (int rc = glue_tau(&g, sampled_tau, dtype == MZ_DT_F16)) return rc;  // as mz_policy_glue
+    glue_dispatch(dtype, g.A, [&](auto f16, auto tiles) {
+        hipLaunchKernelGGL((k_policy_glue_later_rows<decltype(f16)::value, decltype(tiles)::value>),
+                           dim3(g.B, glue + later), dim3(kWave), 0, g.stream, logits, (long long)row_stride,
+                           (const int *)row_agent, g.plan, num_agents, glue, g.use_pow, g.tau_inv, probs_out,
+                           beta_out, (int *)later_out, g.hexp);
+    });
+    return glue_end(g);
+}
+
+int mz_joint_action_cached_rows(mz_batch *b, const int32_t *later_pool, int slots, const int32_t *idx_x,
+                                int num_agents, const int32_t *row_agent, const int32_t *factor, int factor_cols,
+                                const int32_t *actions, int64_t *joint_out) {
+    const char *fn = "mz_joint_action_cached_rows";
+    Glue g;
+    if (int rc = glue_handle(&g, fn, b)) return rc;  // (any A: no row of actions is read)
+    if (int rc = rows_agents(g, num_agents, kMaxGridRows, row_agent)) return rc;
+    if (!actions || !joint_out) return glue_fail(MZ_ERR_ARG, fn, "null buffer");
+    if (int rc = rows_factor(g, num_agents, factor, factor_cols)) return rc;
+    if (num_agents > 1 && (!later_pool || !idx_x || slots < 1))
+        return glue_fail(MZ_ERR_ARG, fn, "later-action pool and idx_x required for later agents");
+    const long long n = (long long)g.B * num_agents;
+    hipLaunchKernelGGL(k_joint_action_cached_rows, dim3((unsigned)((n + kCachedLanes - 1) / kCachedLanes)),
+                       dim3(kCachedLanes), 0, g.stream, (const int *)later_pool, slots, (const int *)idx_x, g.B,
+                       num_agents, (const int *)row_agent, (const int *)factor, factor_cols, (const int *)actions,
                        (long long *)joint_out);
     return glue_end(g);
 }

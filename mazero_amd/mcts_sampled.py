@@ -19,7 +19,9 @@ mz_inverse_transform launch, torch's arithmetic on this device restated bit for 
 model's ~46 torch kernels; with `wide_supports` as well, mz_inverse_transform_wide does the same for
 supports of 65..1024 elements; with `later_action_cache`: the `model.prediction(leaf)` pass goes, the
 later agents' argmax is taken once per node by mz_policy_glue_later, which also does the policy glue,
-and the joint action reads it back through mz_joint_action_cached)
+and the joint action reads it back through mz_joint_action_cached; with `mixed_agents`: a merged
+search whose entries are of different agents takes the current agent from a per-row device table,
+through mz_policy_glue_rows, mz_joint_action_rows, mz_policy_glue_later_rows, mz_joint_action_cached_rows)
 
 (`batch_search_joint` is the one search over joint-action trees that the reference's evaluation loop
 calls, core/test.py:84: trees of agent_num = N, [B, N, A] tree inputs from mz_root_glue_joint and
@@ -136,8 +138,14 @@ class _SearchLoop:
     memory (mz_reseed), so replaying the graph is a new search."""
 
     def __init__(self, tb, B, A, N, cur, hidden, dev, model, root_mode=None, wide=False, fused=None,
-                 wide_supports=False, later_slots=0, joint=False):
+                 wide_supports=False, later_slots=0, joint=False, mixed=False):
         self.tb, self.B, self.A, self.N, self.cur, self.dev = tb, B, A, N, cur, dev
+        # mixed: the rows' searches are of different agents (SampledMCTS's mixed_agents).  The current agent
+        # is device state, the static table row_agent [B] that the _rows glue reads at every launch (cur = 0
+        # is unused), so one recorded graph serves every assignment of agents to rows; fac holds N - 1
+        # columns, of which row i's first row_agent[i] are read.  The loop always runs the later-agents pass:
+        # a row of the last agent takes nothing from it.
+        self.mixed = bool(mixed)
         # joint: one search over the joint-action trees of all N agents (SampledMCTS.batch_search_joint;
         # the handle has agent_num = N).  The tree inputs are [B, N, A], the selection returns every agent's
         # action, so there is no current agent (cur = 0 is unused), no factor and no estimate of the later
@@ -149,7 +157,7 @@ class _SearchLoop:
         # is produced and read by mz_joint_action_cached instead of a prediction pass on the leaf.  The
         # last agent has no later agents: its loop is the default one.
         self.later = None
-        if later_slots and cur + 1 < N:
+        if later_slots and (mixed or cur + 1 < N):
             # (zeros: an action read before its slot was written would still index the model's embedding)
             self.later = torch.zeros(later_slots, B, N, dtype=torch.int32, device=dev)
             # the first search also takes the default path and compares the two joint actions
@@ -174,6 +182,11 @@ class _SearchLoop:
         self.root_glue, self.joint_action, self.policy_glue = (
             getattr(lib, "mz_root_glue" + sfx), getattr(lib, "mz_joint_action" + sfx),
             getattr(lib, "mz_policy_glue" + sfx))
+        if mixed:
+            if not hasattr(lib, "mz_policy_glue_rows"):
+                raise RuntimeError("mixed_agents needs a tree library with mz_policy_glue_rows (include/mzdriver.h, "
+                                   "product library only)")
+            self.row_agent = torch.zeros(B, dtype=torch.int32, device=dev)
         ensure_half_exp(tb._lib, dev.index if dev.index is not None else torch.cuda.current_device())
         self.model_ref = weakref.ref(model)  # the captured graph reads this model's parameters
         # [B, cols] like the caller's hidden state; B is the loop's root count, the driver's root_capacity
@@ -208,7 +221,7 @@ class _SearchLoop:
         self.joint = torch.empty(B, N, dtype=torch.int64, device=dev)
         self.probs = torch.empty(B, RA, dtype=torch.float32, device=dev)
         self.beta = torch.empty(B, RA, dtype=torch.float32, device=dev)
-        self.fac = torch.zeros(B, max(cur, 1), dtype=torch.int32, device=dev)
+        self.fac = torch.zeros(B, max(N - 1 if mixed else cur, 1), dtype=torch.int32, device=dev)
         self.pool = None
         self.leaf = None
         self.pool_ref = None  # the shared _Pool the two above belong to (K > 1)
@@ -239,7 +252,10 @@ class _SearchLoop:
             self.raw_ev.record()
             if dev_logits is not None:
                 self.dev_view["logits"].copy_(dev_logits.reshape(-1))
-        if self.cur > 0:
+        if self.mixed:  # factor: (the rows' agents, their factor columns with zeros behind), on the device
+            self.row_agent.copy_(factor[0])
+            self.fac.copy_(factor[1])
+        elif self.cur > 0:
             if isinstance(factor, torch.Tensor):  # previous agents' actions, already on the device
                 self.fac.copy_(factor[:, : self.cur])
             else:
@@ -276,7 +292,10 @@ class _SearchLoop:
             self.raw_ev.record()
             if dev_logits is not None:
                 fill(self.dev_view["logits"].view(B, -1), dev_logits.reshape(n, -1))
-        if self.cur > 0:
+        if self.mixed:  # (the spare rows are row 0's searches: its agent with its inputs)
+            fill(self.row_agent.view(B, 1), factor[0].view(n, 1))
+            fill(self.fac, factor[1])
+        elif self.cur > 0:
             if not isinstance(factor, torch.Tensor):
                 factor = torch.from_numpy(np.ascontiguousarray(np.asarray(factor)[:, : self.cur], dtype=np.int32))
             fill(self.fac, factor[:, : self.cur])
@@ -336,15 +355,22 @@ class _SearchLoop:
         """mz_policy_glue_later on `logits` [B, N, A]: the later agents' argmax into later[slot], with the
         policy glue of the current agent into probs / beta unless `glue` is False (the root's slot)."""
         logits = logits.contiguous()
-        check(lib, lib.mz_policy_glue_later(h, C.c_void_p(logits.data_ptr()), _dtype_code(logits),
-                                            logits.shape[1] * logits.shape[2], self.N, self.cur, float(tau),
-                                            C.c_void_p(self.probs.data_ptr()) if glue else None,
-                                            C.c_void_p(self.beta.data_ptr()) if glue else None,
-                                            C.c_void_p(self.later[slot].data_ptr())), "policy_glue_later")
+        call, agent = lib.mz_policy_glue_later, self.cur
+        if self.mixed:
+            call, agent = lib.mz_policy_glue_later_rows, C.c_void_p(self.row_agent.data_ptr())
+        check(lib, call(h, C.c_void_p(logits.data_ptr()), _dtype_code(logits), logits.shape[1] * logits.shape[2],
+                        self.N, agent, float(tau), C.c_void_p(self.probs.data_ptr()) if glue else None,
+                        C.c_void_p(self.beta.data_ptr()) if glue else None,
+                        C.c_void_p(self.later[slot].data_ptr())), "policy_glue_later")
 
     def _simulations(self, model, lib, h, leaf, act, B, A, N, cur, K, S, c2, c1, disc, tau, checked=False):
         tb = self.tb
         cached = self.later is not None
+        # the current agent as the glue takes it: the launch constant, or the table of a mixed loop
+        joint_action, joint_action_cached, agent = self.joint_action, lib.mz_joint_action_cached, cur
+        if self.mixed:
+            joint_action, joint_action_cached = lib.mz_joint_action_rows, lib.mz_joint_action_cached_rows
+            agent = C.c_void_p(self.row_agent.data_ptr())
         for s in range(S):
             # later agents' actions from the leaf policy, :136-145: a prediction pass on the leaves, or
             # (later_action_cache) the selected nodes' cached actions; the checked search runs both
@@ -353,21 +379,21 @@ class _SearchLoop:
                 # the selection's [B, N] actions are the whole joint action (:123-124 on joint trees):
                 # widened into the static int64 buffer the model reads; no later agents to estimate
                 self.joint.copy_(act)
-            elif cur + 1 < N and (checked or not cached or s == 0):
+            elif (self.mixed or cur + 1 < N) and (checked or not cached or s == 0):
                 pred_logits, _ = model.prediction(leaf)  # (s == 0: the leaf batch is the root batch)
                 pred_logits = pred_logits.contiguous()
                 ptr, dt = C.c_void_p(pred_logits.data_ptr()), _dtype_code(pred_logits)
                 if cached and s == 0:
                     self._later_glue(lib, h, pred_logits, tau, 0, glue=False)
             if cached:
-                check(lib, lib.mz_joint_action_cached(
+                check(lib, joint_action_cached(
                     h, C.c_void_p(self.later.data_ptr()), self.later.shape[0], C.c_void_p(self.sel[0].data_ptr()),
-                    N, cur, C.c_void_p(self.fac.data_ptr()), self.fac.shape[1], C.c_void_p(act.data_ptr()),
+                    N, agent, C.c_void_p(self.fac.data_ptr()), self.fac.shape[1], C.c_void_p(act.data_ptr()),
                     C.c_void_p((self.joint_cached if checked else self.joint).data_ptr())), "joint_action_cached")
             if (checked or not cached) and not self.joint_mode:
-                check(lib, self.joint_action(h, ptr, dt, N, cur, C.c_void_p(self.fac.data_ptr()),
-                                             self.fac.shape[1], C.c_void_p(act.data_ptr()),
-                                             C.c_void_p(self.joint.data_ptr())), "joint_action")
+                check(lib, joint_action(h, ptr, dt, N, agent, C.c_void_p(self.fac.data_ptr()), self.fac.shape[1],
+                                        C.c_void_p(act.data_ptr()), C.c_void_p(self.joint.data_ptr())),
+                      "joint_action")
             if checked:  # dynamics takes the default joint action below: a mismatch costs nothing but the cache
                 self.mismatch |= (self.joint != self.joint_cached).any()
             r32 = v32 = None
@@ -413,6 +439,12 @@ class _SearchLoop:
                                                     logits.shape[1] * logits.shape[2], N, float(tau),
                                                     C.c_void_p(self.probs.data_ptr()),
                                                     C.c_void_p(self.beta.data_ptr())), "policy_glue_joint")
+            elif self.mixed:  # every row's own agent's logits
+                logits = logits.contiguous()
+                check(lib, lib.mz_policy_glue_rows(h, C.c_void_p(logits.data_ptr()), _dtype_code(logits),
+                                                   logits.shape[1] * logits.shape[2], N, agent, float(tau),
+                                                   C.c_void_p(self.probs.data_ptr()),
+                                                   C.c_void_p(self.beta.data_ptr())), "policy_glue_rows")
             else:
                 logits = logits.contiguous()
                 check(lib, self.policy_glue(h, C.c_void_p(logits.data_ptr()), _dtype_code(logits),
@@ -611,6 +643,8 @@ def _support_bounds(support) -> Tuple[int, int]:
 _DEVICE_OFFSET = "device_root_offset"
 # the place of the current agent in the key of a joint search's loop (no agent index is negative)
 _JOINT_AGENT = -1
+# the place of the current agent in the key of a mixed loop (mixed_agents: the agent is per-row device state)
+_MIXED_AGENTS = "row_agent"
 # the last element of the key of a merged search's loop (batch_search_many: per-segment tree seeds)
 _SEGMENTED = "seed_segments"
 
@@ -630,8 +664,20 @@ class SampledMCTS:
     def __init__(self, config, np_random: np.random.RandomState = None, *, lib=None, use_graph: bool = True,
                  root_shard: Tuple[int, int, int] = None, device_root: bool = True, wide_actions: bool = None,
                  fused_transforms: bool = None, wide_supports: bool = None, later_action_cache: bool = None,
-                 root_capacity: int = None, device_root_offset: bool = None):
-        """`root_capacity` = C: every search of B <= C roots runs on the tree handle and the per-agent
+                 root_capacity: int = None, device_root_offset: bool = None, mixed_agents: bool = None):
+        """`mixed_agents`: batch_search_many takes entries of different agents (`current_agent_idx` a
+        sequence with differing values) and runs them on one loop whose current agent is per-row device
+        state: a static int32 table that the _rows glue entry points read (include/mzdriver.h), so one
+        recorded graph serves every assignment of agents to rows of a geometry.  Entry g equals
+        `batch_search(model, outs[g], cur_g, factors[g], N, legals[g], ...)` bit for bit, under
+        batch_search_many's condition.  The mixed loop always runs the later-agents pass (rows of the last
+        agent take nothing from it).  A call whose entries all name one agent takes the per-agent loop,
+        with the key, the launches and the bytes it has without the flag.  None reads
+        `config.mixed_agents` (False when the config has none).  Off by default: the refusal of entries
+        of different agents is pinned by the test suite.  consume.reanalyze_policy_targets_many runs the
+        agent searches of several reanalyze batches as a wavefront on such loops.
+
+        `root_capacity` = C: every search of B <= C roots runs on the tree handle and the per-agent
         loops (static buffers, recorded graph) of the C-root geometry, so a batch that shrinks and grows
         (self-play searches only the environments still running, selfplay_worker.py:171-211; full-game
         reanalysis searches len(game) roots, reanalyze_worker.py:491-611) keeps replaying one recorded
@@ -761,6 +807,12 @@ class SampledMCTS:
                 raise RuntimeError("root_capacity needs a tree library with mz_set_active_roots "
                                    "(include/mzdriver.h, product library only)")
         self.root_capacity = root_capacity
+        if mixed_agents is None:
+            mixed_agents = getattr(config, "mixed_agents", False)
+        self.mixed_agents = bool(mixed_agents)
+        if self.mixed_agents and lib is not None and not hasattr(lib, "mz_policy_glue_rows"):
+            raise ValueError("mixed_agents needs a tree library with mz_policy_glue_rows (include/mzdriver.h, "
+                             "product library only)")
         self.use_graph = use_graph
         # root preprocessing (softmax, masks, beta) on the device (mz_root_glue); False: in numpy on
         # the host (root_inputs), as the reference computes it
@@ -976,10 +1028,11 @@ class SampledMCTS:
                             _joint, _host_readback)
 
     def _search(self, model, hidden, root_arrays, root_mode, eps, seed, factor, N, cur, sampled_tau, Bc,
-                _joint=False, _host_readback=False, segments=None):
+                _joint=False, _host_readback=False, segments=None, mixed=False):
         """The search behind the root draws: the handle and the loop of Bc roots, the load, the run or the
         replay, the readback.  `segments`: a merged search's (batch_search_many_device), which returns the
-        whole handle's rows."""
+        whole handle's rows.  `mixed`: its rows are of different agents; `factor` is then the pair (the rows'
+        agents, their factor columns) on the device and `cur` is unused."""
         cfg = self.config
         disc = cfg.discount
         A, S = cfg.action_space_size, cfg.num_simulations
@@ -989,7 +1042,8 @@ class SampledMCTS:
             tb = self._tree(Bc, seed, dev, N if _joint else 1, segments)
             # the discount is a kernel argument of the recorded launches; a segmented loop records the
             # prepare kernel that reads the per-tree seed table
-            key = (threading.get_ident(), id(tb), id(model), N, _JOINT_AGENT if _joint else cur, float(eps),
+            key = (threading.get_ident(), id(tb), id(model), N,
+                   _JOINT_AGENT if _joint else _MIXED_AGENTS if mixed else cur, float(eps),
                    float(sampled_tau), float(disc),
                    (Bc,) + tuple(hidden.shape[1:]), hidden.dtype, root_mode, self.wide_actions, self.fused_transforms,
                    self.wide_supports, self.later_action_cache) + (() if segments is None else (_SEGMENTED,))
@@ -1005,7 +1059,7 @@ class SampledMCTS:
                                                    wide=self.wide_actions, fused=self.fused_transforms,
                                                    wide_supports=self.wide_supports,
                                                    later_slots=S + 1 if self.later_action_cache else 0,
-                                                   joint=_joint)
+                                                   joint=_joint, mixed=mixed)
                     st.storage = sig
                 _LOOPS.move_to_end(key)
                 while len(_LOOPS) > max(_MAX_LOOPS, 1):  # least recently used first
@@ -1070,7 +1124,10 @@ class SampledMCTS:
         `later_action_cache`, `wide_actions` and `root_capacity` compose.  `current_agent_idx`,
         `add_noise` and `sampled_tau` may be per-entry sequences; entries that differ in them or in their
         dtypes, a `root_shard`, and sum(B_g) over the capacity raise ValueError before anything launches
-        (the joint search has no merged form: batch_search_joint)."""
+        (the joint search has no merged form: batch_search_joint).  On a `mixed_agents` driver the entries'
+        agents may differ: entry g is then the search of agent current_agent_idx[g], on one loop whose
+        agent is a per-row device table; an agent outside [0, true_num_agents), or an entry of agent
+        cur_g > 0 without a factor of at least cur_g columns, raises ValueError before anything is drawn."""
         whole, bounds = self.batch_search_many_device(model, network_outputs, current_agent_idx, factors,
                                                       true_num_agents, legal_actions_lsts, device, add_noise,
                                                       sampled_tau, draws, _host_readback=True)
@@ -1100,10 +1157,20 @@ class SampledMCTS:
                 return vals[0]
             return x
 
-        cur = int(same(current_agent_idx, "current_agent_idx"))
+        N = int(true_num_agents)
+        # entries of different agents: one loop with the agent per row (mixed_agents); a sequence naming one
+        # agent is that agent's merged search
+        curs = None
+        if self.mixed_agents and isinstance(current_agent_idx, (list, tuple, np.ndarray)):
+            curs = [int(c) for c in current_agent_idx]
+            if len(curs) != G:
+                raise ValueError(f"batch_search_many: {len(curs)} current_agent_idx values for {G} entries")
+            if all(c == curs[0] for c in curs[1:]):
+                curs = None
+        mixed = curs is not None
+        cur = 0 if mixed else int(same(current_agent_idx, "current_agent_idx"))
         add_noise = bool(same(add_noise, "add_noise"))
         sampled_tau = float(same(sampled_tau, "sampled_tau"))
-        N = int(true_num_agents)
         if self.root_shard is not None:
             raise ValueError(f"batch_search_many with root_shard={self.root_shard}: a rank's draws are sliced from "
                              "the whole batch's; merged searches across root shards are not supported")
@@ -1137,17 +1204,25 @@ class SampledMCTS:
             raise ValueError(f"batch_search_many: the entries differ in dtype, device or legal-action form: {kinds}")
         if cur > 0 and any(f is None for f in factors):
             raise ValueError(f"batch_search_many: agent {cur} needs every entry's factor")
+        if mixed:  # (the glue kernels clamp what the table holds; the driver refuses it here)
+            for g, c in enumerate(curs):
+                if not 0 <= c < N:
+                    raise ValueError(f"batch_search_many: entry {g} names agent {c} of {N} (current_agent_idx)")
+                if c > 0 and (factors[g] is None or getattr(factors[g], "ndim", 0) != 2 or factors[g].shape[1] < c):
+                    raise ValueError(f"batch_search_many: entry {g} of agent {c} needs a factor of at least {c} "
+                                     "columns, the previous agents' actions")
 
         # the draws, entry after entry in the reference's order, then each entry's root inputs
         parts, seeds, modes, epss = [], [], [], []
         for g in range(G):
             d = None if draws is None else draws[g]
-            raw = self.root_raw(network_outputs[g], cur, legal_actions_lsts[g], add_noise, draw=d) \
+            cur_g = curs[g] if mixed else cur
+            raw = self.root_raw(network_outputs[g], cur_g, legal_actions_lsts[g], add_noise, draw=d) \
                 if self.device_root else None
             if raw is not None:
                 arrays, mode, eps, seed = raw
             else:
-                (rr, rv, rp, rb, eps, rn), seed = self.root_inputs(network_outputs[g], cur, legal_actions_lsts[g],
+                (rr, rv, rp, rb, eps, rn), seed = self.root_inputs(network_outputs[g], cur_g, legal_actions_lsts[g],
                                                                    add_noise, sampled_tau, draw=d)
                 arrays, mode = (rr, rv, rp, rb, rn), None
             parts.append(arrays)
@@ -1173,6 +1248,15 @@ class SampledMCTS:
         if cur > 0:
             factor = torch.cat([torch.as_tensor(np.ascontiguousarray(_np(f)[:, :cur]) if not isinstance(f, torch.Tensor)
                                                 else f[:, :cur]).to(device=dev, dtype=torch.int32) for f in factors], 0)
+        if mixed:  # the table, and each row's first cur_g factor columns with zeros behind them
+            fac = torch.zeros(total, max(N - 1, 1), dtype=torch.int32, device=dev)
+            lo = 0
+            for c, b, f in zip(curs, sizes, factors):
+                if c > 0:
+                    fac[lo:lo + b, :c] = torch.as_tensor(f[:, :c] if isinstance(f, torch.Tensor) else
+                                                         np.ascontiguousarray(_np(f)[:, :c])).to(dev, torch.int32)
+                lo += b
+            factor = (torch.from_numpy(np.repeat(np.asarray(curs, np.int32), sizes)).to(dev), fac)
         bounds = [0]
         for b in sizes:
             bounds.append(bounds[-1] + b)
@@ -1180,7 +1264,7 @@ class SampledMCTS:
         # continue the last entry's batch, and nobody reads them)
         segments = (bounds[:-1], seeds, [0] * G)
         out = self._search(model, hidden, root_arrays, root_mode, eps, seeds[0], factor, N, cur, sampled_tau, Bc,
-                           False, _host_readback, segments=segments)
+                           False, _host_readback, segments=segments, mixed=mixed)
         return out, bounds
 
     # ---------------------------------------------------------------------------------------
