@@ -11,6 +11,11 @@ oracle, CPU port, pure-Python ptree) consumes byte-identical arrays:
     seed    = rng.choice(256)                   tree seed, drawn after the noise like
                                                 mcts_sampled.py:68,89
 
+`beta = policy` at every non-root node is a property of this benign generator, not of a search:
+a sampling temperature other than 1 makes the two rows differ, and a real network also produces
+exact zeros, subnormals, near-one-hot rows and values far from order one.  tests/edge_inputs.py
+holds those input classes; the edge tests run every kernel family on them.
+
 The root preprocessing (legal mask + 1e-4, renormalisation, beta = mix^(1/tau)) restates
 mcts_sampled.py:64-100 in numpy float32/float64 exactly as the reference driver evaluates it.
 """

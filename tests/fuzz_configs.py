@@ -42,3 +42,43 @@ def fuzz_configs_large(seed: int, n: int):
         eps = float(rng.choice([0.0, 0.25]))
         out.append((B, A, K, S, knobs, lz, False, eps, int(rng.integers(1 << 30))))
     return out
+
+
+def fuzz_edge_configs(seed: int, n: int):
+    """Seeded random small configurations with adversarial network outputs (tests/edge_inputs.py):
+    the knob choices of `fuzz_configs`, one or two input classes applied in the order drawn, to every
+    tree or to a random subset of the trees.  A stream of its own: `fuzz_configs` draws as before."""
+    from edge_inputs import EDGE_CLASSES
+
+    rng = np.random.default_rng(seed)
+    names = sorted(EDGE_CLASSES)
+    out = []
+    for _ in range(n):
+        B = int(rng.integers(1, 9))
+        A = int(rng.choice([2, 9, 17, 64, 100]))
+        K = int(rng.choice([1, 2, 5, 10, 33, 70]))
+        S = int(rng.integers(4, 61))
+        knobs = dict(discount=float(rng.choice([0.997, 0.9, 1.0])), rho=float(rng.choice([0.75, 0.5, 0.0])),
+                     lam=float(rng.choice([0.8, 1.0, 0.5])), delta_lb=float(rng.choice([0.01, 0.1])),
+                     pb_c_init=float(rng.choice([1.25, 2.5])), pb_c_base=float(rng.choice([19652.0, 500.0])))
+        lz = float(rng.choice([0.0, 0.3]))
+        ties = bool(rng.random() < 0.15)
+        eps = float(rng.choice([0.0, 0.25]))
+        classes = [str(c) for c in rng.choice(names, size=int(rng.integers(1, 3)), replace=False)]
+        trees = None
+        if rng.random() < 0.5:
+            trees = sorted(int(t) for t in rng.choice(B, size=int(rng.integers(1, B + 1)), replace=False))
+        out.append((B, A, K, S, knobs, lz, ties, eps, int(rng.integers(1 << 30)), classes, trees))
+    return out
+
+
+def edge_inputs_of(cfg):
+    """The search inputs of one `fuzz_edge_configs` entry."""
+    from dataclasses import replace
+
+    from edge_inputs import apply
+    from mazero_amd.synthetic import make_search_inputs
+
+    B, A, K, S, knobs, lz, ties, eps, s, classes, trees = cfg
+    inp = replace(make_search_inputs(np.random.default_rng(s), B, A, S, legal_zero_frac=lz, ties=ties), noise_eps=eps)
+    return apply(inp, classes, trees)

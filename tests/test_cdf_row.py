@@ -31,6 +31,7 @@ import pytest
 
 import test_chain3_tail as tail
 from conftest import assert_same
+from edge_inputs import masked as _masked
 from test_gpu_parity import _joint_run, gpu_lib, make_tb, run_fused, to_device  # noqa: F401  (gpu_lib: fixture)
 
 torch = pytest.importorskip("torch")
@@ -40,17 +41,6 @@ def _inputs(B, A, S, seed, **kw):
     from mazero_amd.synthetic import make_search_inputs
 
     return make_search_inputs(np.random.default_rng(seed), B, A, S, **kw)
-
-
-def _masked(B, A, S, seed):
-    """40 % zero beta entries on the root's row and on every simulation's (action 1 stays legal)."""
-    inp = _inputs(B, A, S, seed, legal_zero_frac=0.4)
-    legal = np.random.default_rng(seed + 1).random(inp.beta.shape) >= 0.4
-    legal[..., 0] = False
-    legal[..., 1] = True
-    inp = replace(inp, policy=np.where(legal, inp.policy, np.float32(0)), beta=np.where(legal, inp.beta, np.float32(0)))
-    assert (inp.beta == 0).any() and (inp.beta[..., -1] == 0).any()
-    return inp
 
 
 def _check_k(gpu_lib, port_lib, inp, K, kernel, H=4):  # noqa: F811

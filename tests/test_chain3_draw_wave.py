@@ -33,6 +33,7 @@ import pytest
 if __name__ != "__main__":
     import test_chain3_round1 as round1
     import test_chain3_tail as tail
+    from edge_inputs import tiny_tail as _tiny_tail
     from test_gpu_parity import gpu_lib, make_tb, to_device  # noqa: F401  (gpu_lib: fixture)
 
     torch = pytest.importorskip("torch")
@@ -73,12 +74,6 @@ def test_masked_actions(gpu_lib, port_lib):  # noqa: F811
     inp = replace(inp, policy=np.where(legal, inp.policy, np.float32(0)), beta=np.where(legal, inp.beta, np.float32(0)))
     assert (inp.beta == 0).any() and (inp.beta[..., -1] == 0).any()
     _check4(gpu_lib, port_lib, inp)
-
-
-def _tiny_tail(inp):
-    b = inp.beta.copy()
-    b[..., -3:] = b[..., :-3].sum(axis=-1, keepdims=True) * np.float32(1e-30)
-    return replace(inp, beta=b)
 
 
 # ---- the last action: the forced cp = 1.0 (see the module docstring) ----

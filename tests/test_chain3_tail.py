@@ -11,12 +11,12 @@ the error word.  The shapes are the smallest at which the reordered code takes a
 """
 from __future__ import annotations
 
-from dataclasses import replace
-
 import numpy as np
 import pytest
 
 from conftest import assert_same
+from edge_inputs import concentrated as _concentrated  # noqa: F401  (the builders moved; the old names stay)
+from edge_inputs import wild_prior as _wild_prior, wild_reward as _wild_reward, wild_value as _wild_value
 from test_gpu_parity import gpu_lib, make_tb, run_fused, to_device  # noqa: F401  (gpu_lib: fixture)
 
 torch = pytest.importorskip("torch")
@@ -95,14 +95,6 @@ def test_action_classes(gpu_lib, port_lib, A, monkeypatch):
         _check(gpu_lib, port_lib, _inputs(B, A, 6, 1000 + 7 * A + B), monkeypatch=monkeypatch)
 
 
-def _concentrated(inp, j):
-    """beta of every simulation with weight 1 - 1e-6 on action j."""
-    A = inp.A
-    b = np.full(inp.beta.shape, 1e-6 / (A - 1), np.float32)
-    b[..., j] = np.float32(1.0 - 1e-6)
-    return replace(inp, beta=b)
-
-
 # ---- which lane is drawn: the drawn lane's own words, the forced last cp = 1.0 ----
 @pytest.mark.gpu
 @pytest.mark.parametrize("j", [0, 4, 8])
@@ -112,26 +104,6 @@ def test_drawn_lane(gpu_lib, port_lib, j, monkeypatch):
         _check(gpu_lib, port_lib, inp, monkeypatch=monkeypatch)
         exp = _expected(port_lib, inp)
         assert (exp["sel_act"][1:] == j).all()  # (the cases draw what they are named for)
-
-
-def _wild_prior(inp):
-    """policy 1 and beta * 1e-31 from simulation 2 on: every prior (policy / beta) is above 1e30."""
-    p, b = inp.policy.copy(), inp.beta.copy()
-    p[2:] = 1.0
-    b[2:] *= np.float32(1e-31)
-    return replace(inp, policy=p, beta=b)
-
-
-def _wild_value(inp):
-    v = inp.value.copy()
-    v[2] = 1e31
-    return replace(inp, value=v)
-
-
-def _wild_reward(inp):
-    r = inp.reward.copy()
-    r[2] = 1e31
-    return replace(inp, reward=r)
 
 
 # ---- not tame: the exact selection with the barrier ----

@@ -114,6 +114,138 @@ def test_port_matches_reference_fuzz(ref_lib, port_lib, chunk):
             outs.append(run_search(tb, inp, K, knobs))
         assert_same(outs[1], outs[0], f"port vs ref B={B} A={A} K={K} S={S} knobs={knobs}: ")
 
+# ---- adversarial network outputs (tests/edge_inputs.py): the port pinned where the kernels are checked ----
+EDGE_SHAPES = [(1, 9), (5, 9), (10, 100)]  # (K, A)
+
+
+def _edge_base(K, A, B=3, S=40):
+    return make_search_inputs(np.random.default_rng(5000 + 100 * K + A), B, A, S)
+
+
+def _search(lib, inp, K, knobs=None):
+    k = knobs or {}
+    tb = Tree_batch(inp.B, 1, inp.A, K, inp.S, k.get("delta_lb", 0.01), inp.seed, k.get("rho", 0.75),
+                    k.get("lam", 0.8), lib=lib)
+    return run_search(tb, inp, K, knobs)
+
+
+@pytest.mark.parametrize("K,A", EDGE_SHAPES)
+def test_port_matches_reference_edges(ref_lib, port_lib, K, A):
+    """Every input class of tests/edge_inputs.py, on every tree and on tree 1 alone: the reference
+    ctree and the CPU port, bit for bit (the GPU edge tests compare the kernels with the port)."""
+    from edge_inputs import EDGE_CLASSES
+
+    base = _edge_base(K, A)
+    for name, f in EDGE_CLASSES.items():
+        for trees in (None, [1]):
+            inp = f(base, trees)
+            with np.errstate(all="ignore"):
+                outs = [_search(lib, inp, K) for lib in (ref_lib, port_lib)]
+            assert_same(outs[1], outs[0], f"port vs ref {name} trees={trees} K={K} A={A}: ")
+
+
+@pytest.mark.parametrize("chunk", range(int(os.environ.get("MZ_FUZZ_CHUNKS", "4"))))
+def test_port_matches_reference_edge_fuzz(ref_lib, port_lib, chunk):
+    """The GPU edge fuzz configurations (tests/fuzz_configs.py::fuzz_edge_configs), the CPU port
+    against the reference ctree, bit for bit."""
+    from fuzz_configs import edge_inputs_of, fuzz_edge_configs
+
+    for cfg in fuzz_edge_configs(4321 + chunk, 10):
+        B, A, K, S, knobs, lz, ties, eps, s, classes, trees = cfg
+        inp = edge_inputs_of(cfg)
+        with np.errstate(all="ignore"):
+            outs = [_search(lib, inp, K, knobs) for lib in (ref_lib, port_lib)]
+        assert_same(outs[1], outs[0], f"port vs ref B={B} A={A} K={K} S={S} knobs={knobs} lz={lz} ties={ties} "
+                                      f"eps={eps} classes={classes} trees={trees}: ")
+
+
+_INPUT_ARRAYS = ("root_reward", "root_value", "root_policy", "root_beta", "root_noise", "reward", "value", "policy",
+                 "beta")
+
+
+def test_edge_classes_are_what_they_are_named(port_lib):
+    """Each class of tests/edge_inputs.py has the property it is named for, and `trees=[1]` leaves
+    trees 0 and 2 byte-identical to the unmodified inputs."""
+    import edge_inputs as E
+
+    base = _edge_base(1, 9)
+    B, A, S = base.B, base.A, base.S
+    assert np.array_equal(base.beta, base.policy)  # (what the benign generator gives)
+    alt = {name: f(base) for name, f in E.EDGE_CLASSES.items()}
+    for name, f in E.EDGE_CLASSES.items():
+        one = f(base, [1])
+        changed = False
+        for k in _INPUT_ARRAYS:
+            a, b, c = getattr(base, k), getattr(one, k), getattr(alt[name], k)
+            ax = 0 if k.startswith("root_") else 1
+            assert b.dtype == np.float32 and b.shape == a.shape, (name, k)
+            for t in (0, 2):
+                assert np.take(a, t, ax).tobytes() == np.take(b, t, ax).tobytes(), (name, k, t)
+            changed |= np.take(a, 1, ax).tobytes() != np.take(b, 1, ax).tobytes()
+            if name not in ("peaked", "root_peaked"):  # (those draw per call: the same kind, other rows)
+                assert np.take(c, 1, ax).tobytes() == np.take(b, 1, ax).tobytes(), (name, k)
+        assert changed, name
+        assert (one.B, one.A, one.S, one.seed, one.noise_eps) == (B, A, S, base.seed, base.noise_eps)
+    # beta differs from policy, both still distributions, policy untouched
+    for name, tau in (("beta_tau2", 2.0), ("beta_tau05", 0.5)):
+        x = alt[name]
+        assert np.array_equal(x.policy, base.policy) and not np.array_equal(x.beta, x.policy)
+        want = base.policy.astype(np.float64) ** (1 / tau)
+        want /= want.sum(-1, keepdims=True)
+        assert np.allclose(x.beta, want, rtol=1e-5, atol=0) and np.allclose(x.beta.sum(-1), 1, atol=1e-6)
+        assert np.array_equal(np.argsort(x.beta, -1), np.argsort(x.policy, -1))
+    x = alt["beta_rolled"]
+    assert np.array_equal(x.policy, base.policy) and np.array_equal(x.beta[..., :-1], base.policy[..., 1:])
+    assert np.array_equal(x.beta[..., -1], base.policy[..., 0])
+    assert (np.argmax(x.beta, -1) != np.argmax(x.policy, -1)).all()
+    flat, sharp = alt["beta_tau2"].beta.max(-1), alt["beta_tau05"].beta.max(-1)
+    assert (flat < base.policy.max(-1)).all() and (sharp > base.policy.max(-1)).all()
+    # exact zeros; subnormals
+    z = alt["zero_entries"]
+    assert np.array_equal(z.beta == 0, z.policy == 0) and (z.beta[..., 1] > 0).all() and (z.beta[..., -1] == 0).any()
+    assert 0.3 < (z.beta == 0).mean() < 0.5
+    for x, rows in ((alt["peaked"], "policy"), (alt["root_peaked"], "root_policy")):
+        p = getattr(x, rows)
+        assert np.array_equal(p, getattr(x, rows.replace("policy", "beta")))
+        assert (p == 0).any() and np.allclose(p.sum(-1), 1, atol=1e-6) and (p.max(-1) > 0.5).mean() > 0.9
+    p = alt["peaked"].policy
+    assert 0.5 < (p == 0).mean() < 0.7 and 0.02 < E.is_subnormal(p).mean() < 0.12
+    for name, j in (("concentrated_first", 0), ("concentrated_last", A - 1)):
+        b = alt[name].beta
+        assert (b[..., j] > 0.99999).all() and (np.delete(b, j, -1) < 1e-6).all() and (b > 0).all()
+        assert (_search(port_lib, alt[name], 1)["sel_act"][1:] == j).all()  # (K = 1: it draws what it is named for)
+    # wild: a prior above 1e30, a value or a reward outside +-1e30, where stated
+    with np.errstate(all="ignore"):
+        w = alt["wild_prior"]
+        assert (w.policy[2:] / w.beta[2:] > 1e30).all() and np.array_equal(w.policy[:2], base.policy[:2])
+        assert (w.beta[2:] > 0).all() and np.isfinite(w.policy[2:] / w.beta[2:]).any()
+        assert (alt["wild_value"].value[2] > 1e30).all() and np.isfinite(alt["wild_value"].value).all()
+        assert (np.delete(alt["wild_value"].value, 2, 0) == np.delete(base.value, 2, 0)).all()
+        assert (alt["wild_reward"].reward[2] > 1e30).all() and np.isfinite(alt["wild_reward"].reward).all()
+        assert np.isposinf(alt["inf_value"].value[2]).all() and np.isfinite(np.delete(alt["inf_value"].value, 2, 0)).all()
+        assert (alt["root_wild_value"].root_value > 1e30).all()
+        r = alt["root_wild_prior"]
+        assert (r.root_policy / r.root_beta > 1e30).all() and (r.root_beta > 0).all()
+        # (all but the non-root priors reach the root's read-backs: some q or prior past the tame range)
+        for name in (n for n in E.WILD if n != "wild_prior"):
+            out = _search(port_lib, alt[name], 1)
+            far = [np.abs(out[k]).max() for k in ("sampled_qvalues", "sampled_priors", "root_values")]
+            assert max(far) > 1e30 or np.isnan(far).any(), (name, far)
+    for name in E.EDGE_CLASSES:
+        assert not any(np.isnan(getattr(alt[name], k)).any() for k in _INPUT_ARRAYS), name  # (NaN: out of scope)
+    # the normaliser: a spread under delta_lb all search long; magnitudes of the real heads; max == min
+    delta_lb = 0.01
+    for K in (1, 5):
+        out = _search(port_lib, alt["small_spread"], K)
+        for t in range(B):
+            q = np.concatenate([out["sampled_qvalues"][t, : out["degree"][t]], out["root_values"][t : t + 1],
+                                out["root_values_per_sim"][:, t]])
+            assert q.max() - q.min() < delta_lb, (K, t, q.min(), q.max())
+    lg = alt["large_scale"]
+    assert np.abs(lg.value).max() > 300 and np.abs(lg.reward).max() > 20
+    c = alt["constant_value"]
+    assert (c.value == 0.5).all() and (c.reward == 0).all()
+
 
 def test_ptree_joint_action_matches_reference(ref_lib):
     """agent_num = 2 joint-action trees (upstream MAZero semantics)."""
