@@ -61,7 +61,8 @@ int mz_select_actions(mz_batch *b, const int32_t *degrees, const int32_t *visits
  * action actions[i, pos * N .. pos * N + N) -- `roots_sampled_actions[i][action_pos]` of the reference's
  * evaluation loop (core/test.py:101-107, which calls select_action with deterministic=True).  A root
  * without children or visits gets -1 in pos_out and in every column of its action row.  With N = 1 the
- * results are those of mz_select_actions. */
+ * results are those of mz_select_actions.  `width` is any row width >= 1 (one thread walks a root's
+ * row): the 255 children per root of a wide joint handle (mz_create_wide_joint) included. */
 int mz_select_actions_joint(mz_batch *b, const int32_t *degrees, const int32_t *visits, const int32_t *actions,
                             int width, double temperature, int deterministic, const double *uniforms,
                             int32_t *pos_out, int32_t *action_out, double *entropy_out);

@@ -285,6 +285,34 @@ int mz_root_glue_joint(mz_batch *b, const void *logits, int dtype, int64_t row_s
                        const int32_t *legal, int64_t legal_stride, const float *noises, double noise_eps,
                        double sampled_tau, float *probs_out, float *beta_out, float *noises_out);
 
+/* Joint-action trees past 64 actions per agent or 64 sampled joint actions (product library only: the
+ * CPU oracles never had the bound, and mzmcts.h stays what they export).
+ *
+ * mz_create_wide_joint takes mz_create's arguments.  For agent_num = 1, and for agent_num > 1 with
+ * sampled_times <= 64 and action_space_size <= 64, it builds the handle mz_create builds: the same
+ * geometry, the same kernels, the same mz_fused_kernel name.  Past those it builds a wide joint handle:
+ *   action_space_size <= 255   (a joint action is bytes; the node record holds the action in 8 bits)
+ *   sampled_times <= 255       (the node record holds the children count in 8 bits; a joint node has
+ *                               up to min(K, A^N) children)
+ *   agent_num <= 64 and agent_num * action_space_size <= 4096, as mz_create
+ * and everything past them is MZ_ERR_UNSUPPORTED with the bound in the message, before anything is
+ * allocated or launched.  A wide joint handle takes k_prepare's wide joint form for the root and
+ * k_hbm<joint> for every step launch; mz_max_children, the packed readback and
+ * mz_get_roots_sampled_padded follow its wider per-child width.
+ *
+ * mz_policy_glue_joint_wide and mz_root_glue_joint_wide have the signatures, argument checks and
+ * results of mz_policy_glue_joint / mz_root_glue_joint and accept any action_space_size the handle has
+ * (1..255): slice [:, k, :] of every output holds the bytes of mz_policy_glue_wide / mz_root_glue_wide
+ * with col_offset = k * A. */
+int mz_create_wide_joint(int root_num, int agent_num, int action_space_size, int sampled_times, int simulation_num,
+                         float delta_lb, uint32_t random_seed, float rho, float lam, int root_offset,
+                         mz_batch **out);
+int mz_policy_glue_joint_wide(mz_batch *b, const void *logits, int dtype, int64_t row_stride, int num_agents,
+                              double sampled_tau, float *probs_out, float *beta_out);
+int mz_root_glue_joint_wide(mz_batch *b, const void *logits, int dtype, int64_t row_stride, int num_agents,
+                            const int32_t *legal, int64_t legal_stride, const float *noises, double noise_eps,
+                            double sampled_tau, float *probs_out, float *beta_out, float *noises_out);
+
 /* Inverse support transform of the value and the reward head of one simulation: what
  * MAMuZeroNet.recurrent_inference applies to the two heads' logits in eval mode
  * (config/smac/model.py:562-572; core/config.py:430-499: softmax, _inv_phi, _inv_h), both heads in
@@ -363,7 +391,8 @@ int mz_fused_waves(mz_batch *b, int *waves);
 
 /* The kernel this handle launches for mz_prepare and mz_prepare_select, as a NUL-terminated name
  * written into out[len]: "k_prepare1" (agent_num = 1, sampled_times = 1, action_space_size <= 64:
- * the role-specialised kernel, unless MZ_PREPARE_GENERAL is set at mz_create) or "k_prepare". */
+ * the role-specialised kernel, unless MZ_PREPARE_GENERAL is set at mz_create), "k_prepare_wj" (a
+ * wide joint handle of mz_create_wide_joint) or "k_prepare". */
 int mz_prepare_kernel(mz_batch *b, char *out, int len);
 
 /* Release what the library keeps for reuse across handles: device arenas of destroyed handles

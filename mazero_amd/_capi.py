@@ -147,6 +147,11 @@ DRIVER_SIGNATURES = {
     # legal_stride, noises, noise_eps, sampled_tau, probs_out, beta_out, noises_out)
     "mz_policy_glue_joint": (_i, [_p, _p, _i, _i64, _i, C.c_double, _p, _p]),
     "mz_root_glue_joint": (_i, [_p, _p, _i, _i64, _i, _p, _i64, _p, C.c_double, C.c_double, _p, _p, _p]),
+    # joint-action trees past 64 actions per agent or 64 sampled joint actions (A <= 255, K <= 255):
+    # mz_create's arguments, and the two joint glue calls for any A the handle has
+    "mz_create_wide_joint": (_i, [_i, _i, _i, _i, _i, _f, C.c_uint32, _f, _f, _i, C.POINTER(_p)]),
+    "mz_policy_glue_joint_wide": (_i, [_p, _p, _i, _i64, _i, C.c_double, _p, _p]),
+    "mz_root_glue_joint_wide": (_i, [_p, _p, _i, _i64, _i, _p, _i64, _p, C.c_double, C.c_double, _p, _p, _p]),
     # (handle or NULL, stream, stage, n, value head: in, dtype, stride, lo, hi; reward head likewise; outputs)
     "mz_inverse_transform": (_i, [_p, _p, _i, _i, _p, _i, _i64, _i, _i, _p, _i, _i64, _i, _i, _p, _p]),
     "mz_inverse_transform_wide": (_i, [_p, _p, _i, _i, _p, _i, _i64, _i, _i, _p, _i, _i64, _i, _i, _p, _p]),

@@ -1195,13 +1195,13 @@ int mz_joint_action_cached_rows(mz_batch *b, const int32_t *later_pool, int slot
     return glue_end(g);
 }
 
-// The joint glue: k_policy_glue / k_root_glue with an agent per grid row.  One lane per action: joint
-// trees take no more (include/mzmcts.h).
-int mz_policy_glue_joint(mz_batch *b, const void *logits, int dtype, int64_t row_stride, int num_agents,
-                         double sampled_tau, float *probs_out, float *beta_out) {
-    const char *fn = "mz_policy_glue_joint";
+// The joint glue: k_policy_glue / k_root_glue with an agent per grid row.  One lane per action for the
+// _joint entry points (what mz_create's joint trees take); the _joint_wide ones take any A the handle
+// has (`wide`, the trees of mz_create_wide_joint) with the same kernels' wider tile instantiations.
+static int policy_glue_joint(const char *fn, bool wide, mz_batch *b, const void *logits, int dtype, int64_t row_stride,
+                             int num_agents, double sampled_tau, float *probs_out, float *beta_out) {
     Glue g;
-    if (int rc = glue_begin(&g, fn, b, false)) return rc;
+    if (int rc = glue_begin(&g, fn, b, wide)) return rc;
     if (num_agents < 1 || num_agents > kMaxGridRows) return glue_fail(MZ_ERR_ARG, fn, "bad agent count");
     if (!logits || !probs_out || !beta_out) return glue_fail(MZ_ERR_ARG, fn, "null buffer");
     if (int rc = glue_dtype(g, dtype)) return rc;
@@ -1211,12 +1211,12 @@ int mz_policy_glue_joint(mz_batch *b, const void *logits, int dtype, int64_t row
     return launch_policy_glue(g, dtype, num_agents, logits, row_stride, 0, probs_out, beta_out);
 }
 
-int mz_root_glue_joint(mz_batch *b, const void *logits, int dtype, int64_t row_stride, int num_agents,
-                       const int32_t *legal, int64_t legal_stride, const float *noises, double noise_eps,
-                       double sampled_tau, float *probs_out, float *beta_out, float *noises_out) {
-    const char *fn = "mz_root_glue_joint";
+static int root_glue_joint(const char *fn, bool wide, mz_batch *b, const void *logits, int dtype, int64_t row_stride,
+                           int num_agents, const int32_t *legal, int64_t legal_stride, const float *noises,
+                           double noise_eps, double sampled_tau, float *probs_out, float *beta_out,
+                           float *noises_out) {
     Glue g;
-    if (int rc = glue_begin(&g, fn, b, false)) return rc;
+    if (int rc = glue_begin(&g, fn, b, wide)) return rc;
     if (num_agents < 1 || num_agents > kMaxGridRows) return glue_fail(MZ_ERR_ARG, fn, "bad agent count");
     if (!logits || !noises || !probs_out || !beta_out || !noises_out) return glue_fail(MZ_ERR_ARG, fn, "null buffer");
     if (int rc = glue_dtype(g, dtype)) return rc;
@@ -1227,6 +1227,32 @@ int mz_root_glue_joint(mz_batch *b, const void *logits, int dtype, int64_t row_s
     if (int rc = glue_tau(&g, sampled_tau, false)) return rc;  // as mz_root_glue: beta is a float32 array
     return launch_root_glue(g, dtype, num_agents, logits, row_stride, 0, legal, legal_stride, noises, noise_eps,
                             probs_out, beta_out, noises_out);
+}
+
+int mz_policy_glue_joint(mz_batch *b, const void *logits, int dtype, int64_t row_stride, int num_agents,
+                         double sampled_tau, float *probs_out, float *beta_out) {
+    return policy_glue_joint("mz_policy_glue_joint", false, b, logits, dtype, row_stride, num_agents, sampled_tau,
+                             probs_out, beta_out);
+}
+
+int mz_policy_glue_joint_wide(mz_batch *b, const void *logits, int dtype, int64_t row_stride, int num_agents,
+                              double sampled_tau, float *probs_out, float *beta_out) {
+    return policy_glue_joint("mz_policy_glue_joint_wide", true, b, logits, dtype, row_stride, num_agents, sampled_tau,
+                             probs_out, beta_out);
+}
+
+int mz_root_glue_joint(mz_batch *b, const void *logits, int dtype, int64_t row_stride, int num_agents,
+                       const int32_t *legal, int64_t legal_stride, const float *noises, double noise_eps,
+                       double sampled_tau, float *probs_out, float *beta_out, float *noises_out) {
+    return root_glue_joint("mz_root_glue_joint", false, b, logits, dtype, row_stride, num_agents, legal, legal_stride,
+                           noises, noise_eps, sampled_tau, probs_out, beta_out, noises_out);
+}
+
+int mz_root_glue_joint_wide(mz_batch *b, const void *logits, int dtype, int64_t row_stride, int num_agents,
+                            const int32_t *legal, int64_t legal_stride, const float *noises, double noise_eps,
+                            double sampled_tau, float *probs_out, float *beta_out, float *noises_out) {
+    return root_glue_joint("mz_root_glue_joint_wide", true, b, logits, dtype, row_stride, num_agents, legal,
+                           legal_stride, noises, noise_eps, sampled_tau, probs_out, beta_out, noises_out);
 }
 
 int mz_policy_glue(mz_batch *b, const void *logits, int dtype, int64_t row_stride, int64_t col_offset,

@@ -548,9 +548,14 @@ __device__ __forceinline__ void hbm_minmax(const Dev &d, size_t nb, int tot, int
 
 // One simulation step of one tree for pools of any size: [expand + back-propagate (sim s)] ->
 // [select (sim s+1)] -> [gather], as k_step.  JOINT: agent_num > 1 (the leaf's [N][A] inputs and the
-// expansion's per-agent CDFs / draws in dynamic LDS, hbm_lds_bytes).
-template <bool EB, bool SEL, bool JOINT>
+// expansion's per-agent CDFs / draws in dynamic LDS, hbm_lds_bytes).  WJ: the wide joint handles of
+// mz_create_wide_joint (expand_joint_wide, its scratch in dynamic LDS, wide_joint_lds_bytes); the
+// back-propagation, the normaliser and the walk are the same -- the walk scores up to 256 children in
+// four chunks of 64 and takes the k-th listed child across them, and a joint selection's N actions come
+// from J.  The WJ = false instantiations are the kernels they were without the parameter.
+template <bool EB, bool SEL, bool JOINT, bool WJ = false>
 __global__ __launch_bounds__(kHbmWaves * kWave) void k_hbm(const Params *__restrict__ prm, StepArgs a) {
+    static_assert(!WJ || JOINT, "the wide joint expansion is a joint expansion");
     const Geo g = prm->g;
     const Dev d = prm->d;
     extern __shared__ __attribute__((aligned(16))) unsigned char hsm[];
@@ -609,7 +614,12 @@ __global__ __launch_bounds__(kHbmWaves * kWave) void k_hbm(const Params *__restr
             int cursor = h.cursor, ntot = tot;
             long long st_new = 0;
             int nc;
-            if (JOINT) {
+            if constexpr (WJ) {
+                const size_t ib = (size_t)t * g.NA;
+                nc = expand_joint_wide(g, d, t, leaf, a.policy + ib, a.beta + ib, nullptr, 0.f, a.K, v_in, cursor, ntot,
+                                       hsm, err, st_new);
+                h.tame = 0;
+            } else if (JOINT) {
                 const int NA = g.NA;
                 float *jp = (float *)hsm, *jb = jp + NA;
                 double *jcp = (double *)(hsm + ((8 * NA + 15) & ~15));

@@ -1432,6 +1432,150 @@ __device__ int expand_joint(const Geo &g, const Dev &d, int t, int parent, const
 }
 
 // --------------------------------------------------------------------------------------------
+// expand_joint for the handles of mz_create_wide_joint: A <= kWideActions actions per agent and
+// K <= kWideJointK draws (Bn.y packs the action and the children count in 8 bits each).  The same
+// restatement, with every per-draw and per-action quantity taken 64 at a time:
+//   - each agent's distribution by expand_wide's chunked chain (lane l holds actions l + 64 j): the
+//     sequential double sum and the sequential prefix sums in action order, cp[i][a] to LDS;
+//   - the draws in tiles of 64, lane l of tile k0 = draw k0 + l, engine words
+//     cursor + 2 ((k0 + l) N + i), lower_bound a count over the A entries, the key in 64-bit two's
+//     complement; keys [K] and draws [K][N] (bytes) to LDS;
+//   - the distinct keys through LDS: first occurrence and multiplicity in one pass over the K keys,
+//     the rank among the distinct keys in signed order in a second (trip counts K and ceil(K / 64));
+//   - the children in ascending key order, beta_hat = count / K, products over agents in agent order.
+// pol / bet / noi: the node's [N][A] inputs in global memory (noi may be null when eps == 0).
+// smem: wide_joint_lds_bytes() of LDS, 16-byte aligned.
+// --------------------------------------------------------------------------------------------
+constexpr int kWideJointK = 255;
+constexpr int kJointCells = 4096;  // agent_num * action_space_size of a joint tree
+constexpr int kJointAgents = 64;
+__host__ __device__ constexpr int wide_joint_lds_bytes(int NA, int N, int K) {
+    // cp [N][A] double | keys [256] int64 | first-occurrence counts [256] int | draws [K][N] bytes
+    return 8 * NA + 8 * (kWideJointK + 1) + 4 * (kWideJointK + 1) + ((K * N + 15) & ~15);
+}
+static_assert(wide_joint_lds_bytes(kJointCells, kJointAgents, kWideJointK) <= 64 * 1024,
+              "wide joint expansion: LDS scratch of the largest handle");
+
+__device__ int expand_joint_wide(const Geo &g, const Dev &d, int t, int parent, const float *pol, const float *bet,
+                                 const float *noi, float eps, int K, float pv, int &cursor, int &tot,
+                                 unsigned char *smem, int &err, long long &st_new) {
+    const int l = lane_id();
+    const int N = g.N, A = g.A;
+    double *cp = (double *)smem;
+    long long *keys = (long long *)(smem + 8 * g.NA);
+    int *fcnt = (int *)(keys + kWideJointK + 1);
+    unsigned char *draw = (unsigned char *)(fcnt + kWideJointK + 1);
+    if (A >= 2) {
+        for (int i = 0; i < N; ++i) {
+            double w[4];
+#pragma unroll
+            for (int j = 0; j < 4; ++j) w[j] = (64 * j + l < A) ? (double)bet[i * A + 64 * j + l] : 0.0;
+            double sum = 0.0;
+#pragma unroll
+            for (int j = 0; j < 4; ++j)
+                for (int a = 0; a < kWave && 64 * j + a < A; ++a) sum += rld(w[j], a);
+            double acc = 0.0;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const double p = (64 * j + l < A) ? w[j] / sum : 0.0;
+                double c = 0.0;
+                for (int a = 0; a < kWave && 64 * j + a < A; ++a) {
+                    const double pa = rld(p, a);
+                    acc = (j == 0 && a == 0) ? pa : acc + pa;
+                    c = (l == a) ? acc : c;
+                }
+                if (64 * j + l == A - 1) c = 1.0;
+                if (64 * j + l < A) cp[i * A + 64 * j + l] = c;
+            }
+        }
+        wait_lds();
+    }
+    for (int k0 = 0; k0 < K; k0 += kWave) {
+        const int k = k0 + l;
+        if (k < K) {
+            unsigned long long key = 0;
+            for (int i = 0; i < N; ++i) {
+                int act = 0;
+                if (A >= 2) {
+                    const int w = cursor + 2 * (k * N + i);
+                    const double w1 = (double)rng_word_lane(g, d, nullptr, 0, t, w, err);
+                    const double w2 = (double)rng_word_lane(g, d, nullptr, 0, t, w + 1, err);
+                    double u = (w1 + w2 * 4294967296.0) / 18446744073709551616.0;
+                    if (u >= 1.0) u = 0x1.fffffffffffffp-1;  // nextafter(1, 0)
+                    for (int a = 0; a < A; ++a) act += (cp[i * A + a] < u) ? 1 : 0;  // lower_bound
+                }
+                draw[k * N + i] = (unsigned char)act;
+                key = key * 23333ull + (unsigned long long)act;
+            }
+            keys[k] = (long long)key;
+        }
+    }
+    if (A >= 2) cursor += 2 * K * N;
+    wait_lds();
+    // distinct keys, pass 1: draw k's first-occurrence flag and multiplicity (fcnt[k] = the count when
+    // draw k is its key's first occurrence, else 0)
+    int nc = 0;
+    for (int k0 = 0; k0 < K; k0 += kWave) {
+        const int k = k0 + l;
+        const long long sk = (k < K) ? keys[k] : 0;
+        bool first = k < K;
+        int count = 0;
+        for (int j = 0; j < K; ++j) {
+            const long long kj = keys[j];
+            if (k < K && kj == sk) {
+                ++count;
+                if (j < k) first = false;
+            }
+        }
+        if (k < K) fcnt[k] = first ? count : 0;
+        nc += __popcll(ballot(first));
+    }
+    wait_lds();
+    if (tot + nc > g.P) {
+        err |= kErrPool;
+        return 0;
+    }
+    // pass 2: the rank among the distinct keys in signed order (std::map<long>), and the child
+    for (int k0 = 0; k0 < K; k0 += kWave) {
+        const int k = k0 + l;
+        const int count = (k < K) ? fcnt[k] : 0;
+        if (count > 0) {
+            const long long sk = keys[k];
+            int rank = 0;
+            for (int j = 0; j < K; ++j) rank += (fcnt[j] > 0 && keys[j] < sk) ? 1 : 0;
+            const int c = tot + rank;
+            const float bh = (float)count / (float)K;  // betahat_prob = count / sampled_times
+            float beta_prob = 1.0f, pred_prob = 1.0f, prior = 1.0f;
+            for (int i = 0; i < N; ++i) {
+                const int act = draw[k * N + i];
+                const float pa = pol[i * A + act];
+                beta_prob *= bet[i * A + act];
+                pred_prob *= pa;
+                if (eps > 0) {
+                    const float p = pa * (1 - eps) + noi[i * A + act] * eps;
+                    prior *= p;
+                } else {
+                    prior *= pa;
+                }
+            }
+            prior = prior * bh / beta_prob;
+            const size_t gi = (size_t)t * g.P + c;
+            d.A()[gi] = make_int4(0, f2i(prior), f2i(0.0f), f2i(0.0f));
+            d.Bn()[gi] = make_int4(0, pack_y(0, draw[k * N], -1), f2i(0.0f), -1);
+            d.C()[gi] = make_float4(0.f, 0.f, 0.f, 0.f);
+            d.D()[gi] = make_float4(pred_prob, beta_prob, bh, 0.f);
+            d.Q()[gi] = 0.f;
+            d.PP()[gi] = pv;
+            d.Par()[gi] = parent;
+            for (int i = 0; i < N; ++i) d.J()[(size_t)t * g.JP + (size_t)c * N + i] = draw[k * N + i];
+        }
+    }
+    st_new += nc;
+    tot += nc;
+    return nc;
+}
+
+// --------------------------------------------------------------------------------------------
 // Prepare (CTree_batch::prepare, cnode.cpp:589-614 -> CTree::prepare, cnode.cpp:205-222):
 // generate the tree's mt19937 stream (seed random_seed*2333 + i, cnode.cpp:574) with all four
 // waves, then expand the root with wave 0.
@@ -1478,8 +1622,9 @@ __global__ __launch_bounds__(256) void k_seed_table(unsigned *cp, unsigned n) {
     for (unsigned i = threadIdx.x; i < nrows * (kSeedRow / 4); i += 256u) dst[i] = src[i];
 }
 
-// (the body of k_prepare and k_prepare_seg; SEG: the seed value from the per-tree table `seg`)
-template <bool SEG>
+// (the body of k_prepare and k_prepare_seg; SEG: the seed value from the per-tree table `seg`; WJ: the
+// wide joint handles of mz_create_wide_joint, k_prepare_wj / k_prepare_wj_seg)
+template <bool SEG, bool WJ = false>
 __device__ __forceinline__ void prepare_body(const Params *__restrict__ prm, const PrepArgs a,
                                              const uint2 *__restrict__ seg) {
     const Geo g = prm->g;
@@ -1578,7 +1723,7 @@ __device__ __forceinline__ void prepare_body(const Params *__restrict__ prm, con
     // a root expansion that reads engine words past the LDS window (more than kRngWin / 2 engine-word
     // pairs, or the wide expansion, which reads them all from HBM) reads what every wave just stored:
     // a full workgroup barrier (stores drained) first
-    if (g.A > kMaxActions || 2 * a.K * g.N > kRngWin) __syncthreads();
+    if (WJ || g.A > kMaxActions || 2 * a.K * g.N > kRngWin) __syncthreads();
     if (tid >= kWave) return;
     span_end(0, 2);
 
@@ -1593,7 +1738,15 @@ __device__ __forceinline__ void prepare_body(const Params *__restrict__ prm, con
     int nc;
     int first_act = 0;
     int wild = (g.N > 1) ? 1 : 0;  // joint-action trees always take the exact selection
-    if (g.N > 1) {  // joint actions: the root's [N][A] inputs staged in (dynamic) LDS
+    if constexpr (WJ) {  // wide joint actions: the inputs read where they lie, every engine word from HBM
+        extern __shared__ __attribute__((aligned(16))) unsigned char jsm[];
+        const size_t ib = (size_t)t * g.NA;
+        nc = expand_joint_wide(g, d, t, 0, a.policy + ib, a.beta + ib, a.noise ? a.noise + ib : nullptr, a.eps, a.K, v,
+                               cursor, tot, jsm, err, st_new);
+        // (an engine-stream overrun is flagged by the lanes that drew past it)
+        for (unsigned long long m = ballot(err != 0); m; m &= m - 1ull) err |= rl(err, __builtin_ctzll(m));
+        err = uni(err);
+    } else if (g.N > 1) {  // joint actions: the root's [N][A] inputs staged in (dynamic) LDS
         extern __shared__ __attribute__((aligned(16))) unsigned char jsm[];
         const int NA = g.NA;
         float *jp = (float *)jsm, *jb = jp + NA, *jn = jb + NA;
@@ -1695,6 +1848,14 @@ __global__ __launch_bounds__(256) void k_prepare(const Params *__restrict__ prm,
 __global__ __launch_bounds__(256) void k_prepare_seg(const Params *__restrict__ prm, PrepArgs a,
                                                      const uint2 *__restrict__ seg) {
     prepare_body<true>(prm, a, seg);
+}
+// k_prepare / k_prepare_seg for the wide joint handles of mz_create_wide_joint (expand_joint_wide)
+__global__ __launch_bounds__(256) void k_prepare_wj(const Params *__restrict__ prm, PrepArgs a) {
+    prepare_body<false, true>(prm, a, nullptr);
+}
+__global__ __launch_bounds__(256) void k_prepare_wj_seg(const Params *__restrict__ prm, PrepArgs a,
+                                                        const uint2 *__restrict__ seg) {
+    prepare_body<true, true>(prm, a, seg);
 }
 
 // Bootstrap recurrence b = r + disc * b (cnode.cpp:448) over `n` levels, lane-parallel: level
@@ -5859,6 +6020,75 @@ __global__ __launch_bounds__(64) void k_readback(const Params *__restrict__ prm,
     readback_emit(o, disc, Wd, t, g.A, g.N, nc, ra, ca, cb, cd, jt);
 }
 
+// k_readback for the wide joint handles of mz_create_wide_joint: roots of up to kWideJointK children
+// and A <= kWideActions per agent.  The per-child fields go 64 at a time per wave, as readback_wide; the
+// [N][A] marginals from the children's {visits, prior} and joint actions staged in LDS: cell (j, a)
+// sums, in child order, every child whose action for agent j is a (readback_emit's float sum order).
+constexpr int kRbJwThreads = 256;
+__global__ __launch_bounds__(kRbJwThreads) void k_readback_jw(const Params *__restrict__ prm, float disc, int Wd,
+                                                              RbPtrs o) {
+    const Geo g = prm->g;
+    const Dev d = prm->d;
+    __shared__ int s_vis[kWideJointK + 1];
+    __shared__ float s_pri[kWideJointK + 1];
+    __shared__ unsigned char s_j[(kWideJointK + 1) * kJointAgents];
+    const int t = blockIdx.x;
+    const int tid = threadIdx.x;
+    const int N = g.N, A = g.A, NA = g.NA;
+    const size_t nb = (size_t)t * g.P;
+    const int4 ra = d.A()[nb];
+    const int4 rbn = d.Bn()[nb];
+    const int nc = nc_of(rbn.y);
+    const int fc = rbn.x;
+    if (tid == 0) {
+        const int herr = d.hdr()[t].err;  // dead trees re-report their error (see k_prepare)
+        if (herr) atomicOr(d.err(), herr);
+        if (o.values) o.values[t] = (nc > 0) ? i2f(ra.z) : 0.f;
+        if (o.deg) o.deg[t] = nc;
+    }
+    const unsigned char *jt = d.J() + (size_t)t * g.JP + (size_t)fc * N;
+    for (int i = tid; i < Wd; i += kRbJwThreads) {
+        const bool has = i < nc;
+        int4 ca = make_int4(0, 0, 0, 0), cb = ca;
+        float4 cd = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (has) {
+            ca = d.A()[nb + fc + i];
+            cb = d.Bn()[nb + fc + i];
+            cd = d.D()[nb + fc + i];
+        }
+        const size_t r = (size_t)t * Wd + i;
+        const float val = i2f(ca.z), rew = i2f(ca.w);
+        if (int *fa = o.f[MZ_F_ACTIONS])
+            for (int k = 0; k < N; ++k) fa[r * N + k] = has ? (int)jt[i * N + k] : 0;
+        if (o.f[MZ_F_VISIT_COUNT]) o.f[MZ_F_VISIT_COUNT][r] = has ? ca.x : 0;
+        const float fv[MZ_F_COUNT] = {0.f, 0.f, cd.x, cd.y, cd.z, i2f(ca.y), cd.z / cd.y * cd.x, i2f(cb.z), val, rew,
+                                      rew + disc * val};
+#pragma unroll
+        for (int f = MZ_F_PRED_PROBS; f < MZ_F_COUNT; ++f)
+            if (o.f[f]) ((float *)o.f[f])[r] = has ? fv[f] : 0.f;
+    }
+    if (!o.mv && !o.mp) return;
+    for (int i = tid; i < nc; i += kRbJwThreads) {
+        const int4 ca = d.A()[nb + fc + i];
+        s_vis[i] = ca.x;
+        s_pri[i] = i2f(ca.y);
+    }
+    for (int i = tid; i < nc * N; i += kRbJwThreads) s_j[i] = jt[i];
+    __syncthreads();
+    for (int cell = tid; cell < NA; cell += kRbJwThreads) {
+        const int j = cell / A, av = cell - j * A;
+        int mv = 0;
+        float mp = 0.f;
+        for (int c = 0; c < nc; ++c)
+            if ((int)s_j[c * N + j] == av) {
+                mv += s_vis[c];
+                mp += s_pri[c];
+            }
+        if (o.mv) o.mv[(size_t)t * NA + cell] = mv;
+        if (o.mp) o.mp[(size_t)t * NA + cell] = mp;
+    }
+}
+
 // pools past the per-CU LDS image: k_hbm
 #include "mzhbm.inc"
 
@@ -5870,6 +6100,7 @@ __global__ __launch_bounds__(64) void k_readback(const Params *__restrict__ prm,
 struct mz_batch {
     int B, N, A, K, S, P, E, W, PS, Wd;
     int NA;  // N * A: per-root policy / marginal entries
+    bool wj = false;  // a wide joint handle (mz_create_wide_joint past mz_create's joint bounds)
     int active = 0;  // roots [0, active) are what the getters and consumers see (mz_set_active_roots)
     int root_offset = 0;  // host copy of Dev::seed()[1] (mz_create, mz_set_root_offset)
     int device;
@@ -6355,11 +6586,30 @@ void launch_hbm(mz_batch *b, bool eb, bool sel, const StepArgs &a) {
     else launch_hbm_t<false, true, JOINT>(b, a);
 }
 
+template <bool EB, bool SEL>
+void launch_hbm_wj_t(mz_batch *b, const StepArgs &a) {
+    hipLaunchKernelGGL((k_hbm<EB, SEL, true, true>), dim3(b->B), dim3(kHbmWaves * kWave), wide_joint_lds_bytes(b->NA, b->N, b->K),
+                       b->stream, b->prm, a);
+}
+void launch_hbm_wj(mz_batch *b, bool eb, bool sel, const StepArgs &a) {
+    if (eb && sel) launch_hbm_wj_t<true, true>(b, a);
+    else if (eb) launch_hbm_wj_t<true, false>(b, a);
+    else launch_hbm_wj_t<false, true>(b, a);
+}
+// k_readback, or its wide joint form, over the first `roots` trees
+void launch_readback(mz_batch *b, int roots, float disc, const RbPtrs &o) {
+    if (b->wj)
+        hipLaunchKernelGGL(k_readback_jw, dim3(roots), dim3(kRbJwThreads), 0, b->stream, b->prm, disc, b->Wd, o);
+    else
+        hipLaunchKernelGGL(k_readback, dim3(roots), dim3(kWave), 0, b->stream, b->prm, disc, b->Wd, o);
+}
+
 int launch_step(mz_batch *b, bool eb, bool sel, StepArgs a) {
     const Geo &g = b->geo;
     b->dirty = true;
     if (b->hbm) {  // pools past the LDS image: every launch of the handle
-        if (b->N > 1) launch_hbm<true>(b, eb, sel, a);
+        if (b->wj) launch_hbm_wj(b, eb, sel, a);
+        else if (b->N > 1) launch_hbm<true>(b, eb, sel, a);
         else launch_hbm<false>(b, eb, sel, a);
         HIP_TRY(hipGetLastError());
         if (eb) {
@@ -6656,7 +6906,7 @@ int readback_dev(mz_batch *b, float disc) {
     if (b->rb_dev_valid && b->rb_disc == disc) return MZ_OK;
     const RbPtrs o = packed_rb(b);
     b->dirty = true;
-    hipLaunchKernelGGL(k_readback, dim3(b->B), dim3(kWave), 0, b->stream, b->prm, disc, b->Wd, o);
+    launch_readback(b, b->B, disc, o);
     HIP_TRY(hipGetLastError());
     b->rb_dev_valid = true;
     b->rb_valid = false;
@@ -6694,8 +6944,12 @@ const char *mz_last_error(void) { return g_err.c_str(); }
 int mz_abi_version(void) { return MZ_ABI_VERSION; }
 const char *mz_backend(void) { return "hip-gfx950"; }
 
-int mz_create(int B, int N, int A, int K, int S, float delta_lb, uint32_t seed, float rho, float lam, int root_offset,
-              mz_batch **out) {
+}  // extern "C"
+
+namespace {
+// mz_create (wide_joint false) and mz_create_wide_joint
+int create_batch(bool wide_joint, int B, int N, int A, int K, int S, float delta_lb, uint32_t seed, float rho, float lam,
+                 int root_offset, mz_batch **out) {
     if (!out) return fail(MZ_ERR_ARG, "null output handle");
     *out = nullptr;
     if (B < 1 || A < 1 || K < 1 || S < 0) return fail(MZ_ERR_ARG, "bad tree-batch dimensions");
@@ -6704,14 +6958,24 @@ int mz_create(int B, int N, int A, int K, int S, float delta_lb, uint32_t seed, 
     // action spaces past one lane per action (64 < A <= 255) take the wide expansion and k_hbm;
     // Bn.y packs the action and the children count in 8 bits each
     if (A > kWideActions) return fail(MZ_ERR_UNSUPPORTED, "action_space_size > 255");
-    if (N > 1 && (K > kWave || N > kWave || A > kMaxActions || (long long)N * A > 4096))
+    if (N > 1 && !wide_joint && (K > kWave || N > kWave || A > kMaxActions || (long long)N * A > 4096))
         return fail(MZ_ERR_UNSUPPORTED, "joint-action trees (agent_num > 1) need sampled_times <= 64, "
                                          "agent_num <= 64, action_space_size <= 64 and "
                                          "agent_num * action_space_size <= 4096");
+    // mz_create_wide_joint: a joint action is bytes and Bn.y packs the action and the children count
+    // (up to min(K, A^N)) in 8 bits each; past N * A = 4096 nothing could be checked against
+    if (N > 1 && wide_joint) {
+        if (K > kWideJointK)
+            return fail(MZ_ERR_UNSUPPORTED, "wide joint-action trees (agent_num > 1) need sampled_times <= 255");
+        if (N > kJointAgents) return fail(MZ_ERR_UNSUPPORTED, "wide joint-action trees need agent_num <= 64");
+        if ((long long)N * A > kJointCells)
+            return fail(MZ_ERR_UNSUPPORTED, "wide joint-action trees need agent_num * action_space_size <= 4096");
+    }
+    const bool wj = N > 1 && wide_joint && (K > kWave || A > kMaxActions);
     if (S > 65000) return fail(MZ_ERR_UNSUPPORTED, "simulation_num > 65000");
     if (K > (1 << 20)) return fail(MZ_ERR_UNSUPPORTED, "sampled_times > 2^20");
     // max degree of any node: min(K, A^N) (children are the distinct sampled joint actions,
-    // cnode.cpp:242-294)
+    // cnode.cpp:242-294); the power saturates: an stops at the first product >= K, at most K * A
     int Wd = 1;
     {
         long long an = 1;
@@ -6734,6 +6998,7 @@ int mz_create(int B, int N, int A, int K, int S, float delta_lb, uint32_t seed, 
     b->N = N;
     b->A = A;
     b->NA = N * A;
+    b->wj = wj;
     b->K = K;
     b->S = S;
     b->P = (int)P;
@@ -6845,7 +7110,7 @@ int mz_create(int B, int N, int A, int K, int S, float delta_lb, uint32_t seed, 
     // a pool whose LDS image does not fit one CU (or MZ_HBM=1 at mz_create, for tests): every step
     // launch of the handle is k_hbm, which keeps the tree in the arena (the reference allocates
     // K * (S + 2) nodes for any K and S, cnode.cpp:553-577)
-    b->hbm = g.lds > 160 * 1024 || A > kMaxActions || K > 4096 || getenv_flag("MZ_HBM");
+    b->hbm = g.lds > 160 * 1024 || A > kMaxActions || K > 4096 || wj || getenv_flag("MZ_HBM");
     if (b->hbm) b->nc = 0;
     if (!b->hbm && K == 1 && N == 1 && !getenv_flag("MZ_NO_CHAIN")) {
         b->chain_nc = 0;
@@ -6978,7 +7243,17 @@ int mz_create(int B, int N, int A, int K, int S, float delta_lb, uint32_t seed, 
             return fail(MZ_ERR_DEVICE, "device initialisation failed");
         }
     }
-    if (b->hbm) {
+    if (wj) {  // the wide joint expansion's scratch (k_prepare_wj*, k_hbm<.., joint, wide>)
+        const int wl = wide_joint_lds_bytes(b->NA, N, K);
+        if (wl > 48 * 1024) {
+            const auto attr = hipFuncAttributeMaxDynamicSharedMemorySize;
+            (void)hipFuncSetAttribute((const void *)k_prepare_wj, attr, wl);
+            (void)hipFuncSetAttribute((const void *)k_prepare_wj_seg, attr, wl);
+            (void)hipFuncSetAttribute((const void *)k_hbm<true, true, true, true>, attr, wl);
+            (void)hipFuncSetAttribute((const void *)k_hbm<true, false, true, true>, attr, wl);
+            (void)hipFuncSetAttribute((const void *)k_hbm<false, true, true, true>, attr, wl);
+        }
+    } else if (b->hbm) {
         const int hl = hbm_lds_bytes(N, b->NA);
         if (hl > 48 * 1024) {
             const auto attr = hipFuncAttributeMaxDynamicSharedMemorySize;
@@ -6987,7 +7262,7 @@ int mz_create(int B, int N, int A, int K, int S, float delta_lb, uint32_t seed, 
             (void)hipFuncSetAttribute((const void *)k_hbm<false, true, true>, attr, hl);
         }
     }
-    if (N > 1) {  // k_prepare's dynamic LDS for the root's joint inputs (mz_prepare)
+    if (N > 1 && !wj) {  // k_prepare's dynamic LDS for the root's joint inputs (mz_prepare)
         const int jl = ((12 * b->NA + 15) & ~15) + 8 * b->NA + 4 * kWave * N;
         if (jl > 48 * 1024) {
             (void)hipFuncSetAttribute((const void *)k_prepare, hipFuncAttributeMaxDynamicSharedMemorySize, jl);
@@ -7036,6 +7311,20 @@ int mz_create(int B, int N, int A, int K, int S, float delta_lb, uint32_t seed, 
     }
     *out = b;
     return MZ_OK;
+}
+}  // namespace
+
+extern "C" {
+
+int mz_create(int B, int N, int A, int K, int S, float delta_lb, uint32_t seed, float rho, float lam, int root_offset,
+              mz_batch **out) {
+    return create_batch(false, B, N, A, K, S, delta_lb, seed, rho, lam, root_offset, out);
+}
+
+// include/mzdriver.h
+int mz_create_wide_joint(int B, int N, int A, int K, int S, float delta_lb, uint32_t seed, float rho, float lam,
+                         int root_offset, mz_batch **out) {
+    return create_batch(true, B, N, A, K, S, delta_lb, seed, rho, lam, root_offset, out);
 }
 
 int mz_destroy(mz_batch *b) {
@@ -7109,6 +7398,15 @@ void launch_prepare(mz_batch *b, const PrepArgs &a, size_t jl) {
         }
         hipLaunchKernelGGL(k_prepare1, dim3(b->B), dim3(kPrep1Waves * kWave), 0, b->stream, (char *)b->dev.base,
                            a.reward, a.value, a.policy, a.beta, a.noise, bak, pps, io);
+        return;
+    }
+    if (b->wj) {  // (its scratch, not the staged inputs `jl` counts)
+        const size_t wl = (size_t)wide_joint_lds_bytes(b->NA, b->N, b->K);
+        if (seg)
+            hipLaunchKernelGGL(k_prepare_wj_seg, dim3(b->B), dim3(256), wl, b->stream, b->prm, a,
+                               (const uint2 *)b->seg_tab);
+        else
+            hipLaunchKernelGGL(k_prepare_wj, dim3(b->B), dim3(256), wl, b->stream, b->prm, a);
         return;
     }
     if (seg) {
@@ -7466,7 +7764,7 @@ int mz_fused_waves(mz_batch *b, int *waves) {
 
 int mz_prepare_kernel(mz_batch *b, char *out, int len) {
     if (!b || !out || len < 1) return fail(MZ_ERR_ARG, "mz_prepare_kernel: null argument");
-    std::snprintf(out, (size_t)len, "%s", b->prep1 ? "k_prepare1" : "k_prepare");
+    std::snprintf(out, (size_t)len, "%s", b->prep1 ? "k_prepare1" : b->wj ? "k_prepare_wj" : "k_prepare");
     return MZ_OK;
 }
 
@@ -7532,7 +7830,7 @@ int mz_get_roots_device(mz_batch *b, float discount, const mz_readback_out *out)
     for (int f = 0; f < MZ_F_COUNT; ++f) o.f[f] = (int *)out->sampled[f];
     b->dirty = true;
     // one workgroup per root: the caller's buffers hold rows [0, active) (mz_set_active_roots)
-    hipLaunchKernelGGL(k_readback, dim3(b->active), dim3(kWave), 0, b->stream, b->prm, discount, b->Wd, o);
+    launch_readback(b, b->active, discount, o);
     HIP_TRY(hipGetLastError());
     return MZ_OK;
 }
@@ -7574,7 +7872,7 @@ int mz_expand_backup_readback(mz_batch *b, int hsx, float discount, int K, const
     if (rc) return rc;
     if (!slot) {
         b->dirty = true;
-        hipLaunchKernelGGL(k_readback, dim3(b->B), dim3(kWave), 0, b->stream, b->prm, readback_discount, b->Wd, o);
+        launch_readback(b, b->B, readback_discount, o);
         HIP_TRY(hipGetLastError());
     }
     if (!out) {  // the packed buffer now mirrors the trees

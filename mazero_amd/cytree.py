@@ -97,17 +97,26 @@ class Tree_batch:
         *,
         root_offset: int = 0,
         lib=None,
+        wide_joint: bool = False,
     ):
+        """wide_joint: build the handle with mz_create_wide_joint (include/mzdriver.h): joint-action trees
+        (agent_num > 1) of up to 255 actions per agent and 255 sampled joint actions; inside mz_create's
+        bounds the handle is mz_create's.  A library without that entry point (an oracle, which never
+        had the bounds) keeps mz_create."""
         if lib is None:
             from ._lib import load
 
             lib = load()
         self._lib = lib
+        self.wide_joint = bool(wide_joint)
+        create = lib.mz_create
+        if self.wide_joint and hasattr(lib, "mz_create_wide_joint"):
+            create = lib.mz_create_wide_joint
         self.root_num = int(root_num)
         self.agent_num = int(agent_num)
         self.action_space_size = int(action_space_size)
         self._h = C.c_void_p()
-        rc = lib.mz_create(
+        rc = create(
             self.root_num,
             self.agent_num,
             self.action_space_size,

@@ -138,7 +138,7 @@ class _SearchLoop:
     memory (mz_reseed), so replaying the graph is a new search."""
 
     def __init__(self, tb, B, A, N, cur, hidden, dev, model, root_mode=None, wide=False, fused=None,
-                 wide_supports=False, later_slots=0, joint=False, mixed=False):
+                 wide_supports=False, later_slots=0, joint=False, mixed=False, wide_joint=False):
         self.tb, self.B, self.A, self.N, self.cur, self.dev = tb, B, A, N, cur, dev
         # mixed: the rows' searches are of different agents (SampledMCTS's mixed_agents).  The current agent
         # is device state, the static table row_agent [B] that the _rows glue reads at every launch (cur = 0
@@ -151,6 +151,11 @@ class _SearchLoop:
         # action, so there is no current agent (cur = 0 is unused), no factor and no estimate of the later
         # agents' actions; the glue is the _joint entry points, every agent's row in one launch.
         self.joint_mode = bool(joint)
+        # wide_joint (SampledMCTS's): the _joint_wide glue, which takes any A the handle has (A <= 255)
+        jsfx = "_joint_wide" if wide_joint else "_joint"
+        if joint:
+            self.root_glue_joint = getattr(tb._lib, "mz_root_glue" + jsfx)
+            self.policy_glue_joint = getattr(tb._lib, "mz_policy_glue" + jsfx)
         R = N if joint else 1  # rows of A actions per root in the tree's policy / beta / noise inputs
         # later_slots = S + 1 (SampledMCTS's later_action_cache; 0: off): the later agents' greedy actions
         # of every node, slot hidden_state_index_x, filled by mz_policy_glue_later when the node's state
@@ -316,11 +321,11 @@ class _SearchLoop:
             dv = self.dev_view
             lg = dv.get("legal")
             if self.joint_mode:  # every agent's row: [B, N, A] in, [B, N, A] out
-                check(lib, lib.mz_root_glue_joint(h, C.c_void_p(dv["logits"].data_ptr()), self.root_mode[0], N * A,
-                                                  N, None if lg is None else C.c_void_p(lg.data_ptr()), N * A,
-                                                  C.c_void_p(dv["noise"].data_ptr()), float(eps), float(tau),
-                                                  C.c_void_p(r[2].data_ptr()), C.c_void_p(r[3].data_ptr()),
-                                                  C.c_void_p(r[4].data_ptr())), "root_glue_joint")
+                check(lib, self.root_glue_joint(h, C.c_void_p(dv["logits"].data_ptr()), self.root_mode[0], N * A,
+                                                N, None if lg is None else C.c_void_p(lg.data_ptr()), N * A,
+                                                C.c_void_p(dv["noise"].data_ptr()), float(eps), float(tau),
+                                                C.c_void_p(r[2].data_ptr()), C.c_void_p(r[3].data_ptr()),
+                                                C.c_void_p(r[4].data_ptr())), "root_glue_joint")
             else:
                 check(lib, self.root_glue(h, C.c_void_p(dv["logits"].data_ptr()), self.root_mode[0], A, 0,
                                           None if lg is None else C.c_void_p(lg.data_ptr()), A,
@@ -435,10 +440,10 @@ class _SearchLoop:
                     raise ValueError(f"joint search: policy logits of shape {tuple(logits.shape)} for {N} agents "
                                      f"and {A} actions")
                 logits = logits.contiguous()
-                check(lib, lib.mz_policy_glue_joint(h, C.c_void_p(logits.data_ptr()), _dtype_code(logits),
-                                                    logits.shape[1] * logits.shape[2], N, float(tau),
-                                                    C.c_void_p(self.probs.data_ptr()),
-                                                    C.c_void_p(self.beta.data_ptr())), "policy_glue_joint")
+                check(lib, self.policy_glue_joint(h, C.c_void_p(logits.data_ptr()), _dtype_code(logits),
+                                                  logits.shape[1] * logits.shape[2], N, float(tau),
+                                                  C.c_void_p(self.probs.data_ptr()),
+                                                  C.c_void_p(self.beta.data_ptr())), "policy_glue_joint")
             elif self.mixed:  # every row's own agent's logits
                 logits = logits.contiguous()
                 check(lib, lib.mz_policy_glue_rows(h, C.c_void_p(logits.data_ptr()), _dtype_code(logits),
@@ -664,8 +669,17 @@ class SampledMCTS:
     def __init__(self, config, np_random: np.random.RandomState = None, *, lib=None, use_graph: bool = True,
                  root_shard: Tuple[int, int, int] = None, device_root: bool = True, wide_actions: bool = None,
                  fused_transforms: bool = None, wide_supports: bool = None, later_action_cache: bool = None,
-                 root_capacity: int = None, device_root_offset: bool = None, mixed_agents: bool = None):
-        """`mixed_agents`: batch_search_many takes entries of different agents (`current_agent_idx` a
+                 root_capacity: int = None, device_root_offset: bool = None, mixed_agents: bool = None,
+                 wide_joint: bool = None):
+        """`wide_joint`: batch_search_joint builds its trees with mz_create_wide_joint and runs the
+        _joint_wide glue (include/mzdriver.h): joint-action trees of up to 255 actions per agent and 255
+        sampled joint actions (agent_num <= 64, agent_num * action_space_size <= 4096), instead of 64 and
+        64.  Inside the narrow bounds the handle and its kernels are those of the search without the flag.
+        The constructor then accepts action_space_size <= 255, as with `wide_actions`.  None reads
+        `config.wide_joint` (False when the config has none).  Off by default: the refusals of the joint
+        search are pinned by the test suite.  The per-agent searches are unchanged by it.
+
+        `mixed_agents`: batch_search_many takes entries of different agents (`current_agent_idx` a
         sequence with differing values) and runs them on one loop whose current agent is per-row device
         state: a static int32 table that the _rows glue entry points read (include/mzdriver.h), so one
         recorded graph serves every assignment of agents to rows of a geometry.  Entry g equals
@@ -747,7 +761,10 @@ class SampledMCTS:
         if wide_actions is None:
             wide_actions = getattr(config, "wide_actions", False)
         self.wide_actions = bool(wide_actions)
-        if self.wide_actions:
+        if wide_joint is None:
+            wide_joint = getattr(config, "wide_joint", False)
+        self.wide_joint = bool(wide_joint)
+        if self.wide_actions or self.wide_joint:
             if int(config.action_space_size) > MAX_WIDE_ACTIONS:
                 raise RuntimeError(f"SampledMCTS: action_space_size {config.action_space_size} > {MAX_WIDE_ACTIONS} "
                                    "(a tree node packs its action in 8 bits; the wide driver glue and "
@@ -943,9 +960,10 @@ class SampledMCTS:
         """One double per root in root order, as B np_random.choice(n, p) calls draw them."""
         return np.asarray(self.draw_rows(lambda n: self.np_random.random(n), B), dtype=np.float64)
 
-    def _tree(self, B, seed, device, agent_num: int = 1, segments=None):
+    def _tree(self, B, seed, device, agent_num: int = 1, segments=None, wide_joint: bool = False):
         """The cached handle of this geometry, reseeded.  `agent_num` > 1: joint-action trees
-        (batch_search_joint); what the handle refuses (A > 64, K > 64, N * A > 4096) raises here.
+        (batch_search_joint); what the handle refuses (A > 64, K > 64, N * A > 4096; with `wide_joint`,
+        Tree_batch's, A > 255, K > 255, N * A > 4096) raises here.
         `segments` = (first_tree, seeds, root_offsets): the trees of several searches
         (Tree_batch.set_seed_segments)."""
         cfg = self.config
@@ -954,7 +972,8 @@ class SampledMCTS:
         key = (threading.get_ident(), B, cfg.action_space_size, cfg.sampled_action_times, cfg.num_simulations,
                float(cfg.tree_value_stat_delta_lb), float(cfg.mcts_rho), float(cfg.mcts_lambda),
                float(cfg.pb_c_base), float(cfg.pb_c_init), str(device), id(self._lib),
-               _DEVICE_OFFSET if self.device_root_offset else self._root_offset(), int(agent_num))
+               _DEVICE_OFFSET if self.device_root_offset else self._root_offset(), int(agent_num),
+               bool(wide_joint))
         with _LOCK:
             tb = _TREES.get(key)
             if tb is None:
@@ -962,7 +981,7 @@ class SampledMCTS:
                                 cfg.num_simulations,
                                 cfg.tree_value_stat_delta_lb, int(seed), cfg.mcts_rho, cfg.mcts_lambda,
                                 root_offset=0 if self.device_root_offset else self._root_offset(),
-                                lib=self._lib)
+                                lib=self._lib, wide_joint=bool(wide_joint))
                 _TREES[key] = tb
                 while len(_TREES) > max(_MAX_TREES, 1):  # least recently used first, with its loops
                     _, old = _TREES.popitem(last=False)
@@ -1039,14 +1058,15 @@ class SampledMCTS:
         dev = hidden.device
         B = hidden.shape[0]
         with torch.cuda.device(dev):
-            tb = self._tree(Bc, seed, dev, N if _joint else 1, segments)
+            wide_joint = bool(_joint and self.wide_joint)
+            tb = self._tree(Bc, seed, dev, N if _joint else 1, segments, wide_joint)
             # the discount is a kernel argument of the recorded launches; a segmented loop records the
             # prepare kernel that reads the per-tree seed table
             key = (threading.get_ident(), id(tb), id(model), N,
                    _JOINT_AGENT if _joint else _MIXED_AGENTS if mixed else cur, float(eps),
                    float(sampled_tau), float(disc),
-                   (Bc,) + tuple(hidden.shape[1:]), hidden.dtype, root_mode, self.wide_actions, self.fused_transforms,
-                   self.wide_supports, self.later_action_cache) + (() if segments is None else (_SEGMENTED,))
+                   (Bc,) + tuple(hidden.shape[1:]), hidden.dtype, root_mode, wide_joint, self.wide_actions,
+                   self.fused_transforms, self.wide_supports, self.later_action_cache) + (() if segments is None else (_SEGMENTED,))
             with _LOCK:
                 for k in [k for k, v in _LOOPS.items() if v.model_ref() is None]:
                     del _LOOPS[k]  # loops (graph, pool) of models that no longer exist
@@ -1059,7 +1079,7 @@ class SampledMCTS:
                                                    wide=self.wide_actions, fused=self.fused_transforms,
                                                    wide_supports=self.wide_supports,
                                                    later_slots=S + 1 if self.later_action_cache else 0,
-                                                   joint=_joint, mixed=mixed)
+                                                   joint=_joint, mixed=mixed, wide_joint=wide_joint)
                     st.storage = sig
                 _LOOPS.move_to_end(key)
                 while len(_LOOPS) > max(_MAX_LOOPS, 1):  # least recently used first
@@ -1291,7 +1311,9 @@ class SampledMCTS:
         mz_policy_glue_joint, around the fused tree kernel; the first search is eager, later ones replay
         one recorded graph.  `fused_transforms`, `wide_supports` and `root_shard` compose;
         `root_capacity`, `later_action_cache` and `wide_actions` raise ValueError.  What the tree handle
-        refuses for N > 1 (A > 64, K > 64, N * A > 4096) raises from Tree_batch before anything launches."""
+        refuses for N > 1 (A > 64, K > 64, N * A > 4096) raises from Tree_batch before anything launches.
+        With the constructor's `wide_joint` the handle is mz_create_wide_joint's and the glue the
+        _joint_wide entry points: A <= 255 and K <= 255 (N <= 64, N * A <= 4096)."""
         return self.batch_search_joint_device(model, network_output, legal_actions_lst, device, add_noise,
                                               sampled_tau, sampled_actions_res, _host_readback=True)
 
@@ -1306,7 +1328,8 @@ class SampledMCTS:
                 raise ValueError(f"batch_search_joint does not take {flag}: " + {
                     "root_capacity": "the padded loop is the per-agent one",
                     "later_action_cache": "a joint search estimates no later agents' actions",
-                    "wide_actions": "joint-action trees take at most 64 actions per agent"}[flag])
+                    "wide_actions": "joint-action trees take at most 64 actions per agent "
+                                    "(wide_joint: up to 255)"}[flag])
         logits = network_output.policy_logits
         if getattr(logits, "ndim", 0) != 3:
             raise ValueError("network_output.policy_logits must be [B, num_agents, A]")
