@@ -47,10 +47,28 @@ extern "C" {
  *                                    (ignored when deterministic)
  *   pos_out   int32 [B]   chosen child; action_out int32 [B] its action for agent 0;
  *   entropy_out float64 [B] scipy.stats.entropy(action_probs, base=2) (may be NULL).
- * probs = v ** (1 / temperature) / sum(...): exact repeated products when 1/temperature is an
- * integer up to 8 (the reference's schedule uses 1, 2, 4; config.py:392-401), else the device pow.
+ * probs = v ** (1 / temperature) / sum(...), where v ** e is Python's float power of an int, the
+ * host libm's pow (mz_select_pow_plan below says which of the two ways a count takes):
+ *   - e an integer in 1..8 and v ** e <= 2**53 (e = 1: every v; 2: v <= 94,906,265; 3: 208,063;
+ *     4: 9,741; 5: 1,552; 6: 456; 7: 190; 8: 98): the repeated product in the kernel, whose every
+ *     partial product is an integer below 2**53, hence exact and equal to pow.  The reference's
+ *     schedule (1/temperature = 1, 2, 4; config.py:392-401) with counts in that range runs as it
+ *     always did: no table, no upload.
+ *   - every other count up to MZ_SELECT_POW_TABLE_MAX, for every other temperature and for e = 4..8
+ *     past the bound: a table of pow((double)v, e) computed by the host's libm, uploaded on first use
+ *     of an e on a device and kept (16 per process): make the first call for a temperature outside any
+ *     stream capture (MZ_ERR_RUNTIME inside one).  The device pow is not used: it is not libm's, and
+ *     with it the kernel chose another child than numpy at 18 to 447 of about 2,600 boundary draws in
+ *     every class tried (1/temperature = 10; temperatures 0.3, 0.7, 1.5, 2.0; the table is in
+ *     tests/test_consume_edges.py).
  * A root without children or without visits gets -1 (the reference asserts / draws from the
- * legal actions instead; neither happens after num_simulations >= 1).
+ * legal actions instead; neither happens after num_simulations >= 1).  So does a root of a degree
+ * past `width`, a root holding a count that neither way covers (past the product's bound with e = 1..3,
+ * past MZ_SELECT_POW_TABLE_MAX otherwise, or negative outside the product), and a root whose powers
+ * sum to infinity: -1 in pos_out and action_out and a NaN entropy, never an inexact answer.
+ * tests/test_consume_edges.py checks pos and action at every cdf entry and its two float64 neighbours
+ * (1/temperature = 1..8 and 10, temperatures 0.3, 0.7, 1.5, 2.0, counts up to 3,000, and up to 20,000
+ * at 0.25; rows of 1 to 255 children) against numpy's cumsum / searchsorted.
  * B = the handle's active roots (mz_set_active_roots): every buffer holds B rows. */
 int mz_select_actions(mz_batch *b, const int32_t *degrees, const int32_t *visits, const int32_t *actions,
                       int width, double temperature, int deterministic, const double *uniforms, int32_t *pos_out,
@@ -66,6 +84,21 @@ int mz_select_actions(mz_batch *b, const int32_t *degrees, const int32_t *visits
 int mz_select_actions_joint(mz_batch *b, const int32_t *degrees, const int32_t *visits, const int32_t *actions,
                             int width, double temperature, int deterministic, const double *uniforms,
                             int32_t *pos_out, int32_t *action_out, double *entropy_out);
+
+/* The largest visit count of the host-made power table of mz_select_actions. */
+#define MZ_SELECT_POW_TABLE_MAX 65535
+
+/* How mz_select_actions computes v ** (1 / temperature) (host only: no device call):
+ *   *ipow        the exponent of the in-kernel repeated product, 1..8, or 0 when 1/temperature is no
+ *                integer in that range;
+ *   *exact_max   the largest v the product is used for: the largest int32 v with v ** ipow <= 2**53,
+ *                found in integer arithmetic from the exponent alone (-1 when *ipow == 0);
+ *   *uses_table  1 when some count in 0..MZ_SELECT_POW_TABLE_MAX lies past exact_max, i.e. the call
+ *                uploads the table; 0 otherwise (1/temperature = 1, 2, 3);
+ *   table        (may be NULL) table_len <= MZ_SELECT_POW_TABLE_MAX + 1 doubles: table[v] = the
+ *                uploaded table's entry, pow((double)v, 1 / temperature) by the host's libm. */
+int mz_select_pow_plan(double temperature, int32_t *ipow, int32_t *exact_max, int32_t *uses_table, double *table,
+                       int table_len);
 
 /* eps_greedy_action(greedy, legal_mask, eps) (core/utils.py:319-334) for every root:
  *   action_io = (u_eps[i] < (float)eps) ? categorical(legal[i, :]; u_cat[i]) : action_io[i]

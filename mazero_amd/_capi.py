@@ -176,6 +176,8 @@ MZ_MARGINAL_GIVEN, MZ_MARGINAL_ARGMAX, MZ_MARGINAL_ARGMAX_LEGAL = 0, 1, 2  # enu
 CONSUME_SIGNATURES = {
     "mz_select_actions": (_i, [_p, _p, _p, _p, _i, C.c_double, _i, _p, _p, _p, _p]),
     "mz_select_actions_joint": (_i, [_p, _p, _p, _p, _i, C.c_double, _i, _p, _p, _p, _p]),  # action_out [B, N]
+    # (temperature, ipow, exact_max, uses_table, table or NULL, table_len): host only
+    "mz_select_pow_plan": (_i, [C.c_double, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32), _p, _i]),
     "mz_eps_greedy": (_i, [_p, _p, _i64, _f, _p, _p, _p]),
     "mz_marginal_policy": (_i, [_p, _p, _i64, _p, _i64, _i, _p, _p, _p]),
     # reanalyze batch targets: (handle or NULL, stream, ...)

@@ -77,7 +77,10 @@ def select_actions(out: DeviceSearchOutput, uniforms: Optional[torch.Tensor], te
                    deterministic: bool = False) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
     """select_action (core/utils.py:289-316) at every root -> (pos, agent-0 action, count
     entropy), int32 / int32 / float64 [B] device tensors.  `uniforms`: float64 [B], the doubles
-    `np_random.choice` would draw, in root order (unused when deterministic)."""
+    `np_random.choice` would draw, in root order (unused when deterministic).  A root the kernel cannot
+    answer exactly (no children or visits, or a count past what its powers cover: include/mzconsume.h)
+    gets -1 and a NaN entropy.  Outside 1/temperature = 1, 2, 3 the first call for a temperature uploads
+    a table and must be made outside any graph capture."""
     tb = _tree(out)
     visits = out.sampled["visit_count"].contiguous()
     actions = out.sampled["actions"].contiguous()
@@ -91,9 +94,11 @@ def select_actions(out: DeviceSearchOutput, uniforms: Optional[torch.Tensor], te
     act = torch.empty(B, dtype=torch.int32, device=dev)
     ent = torch.empty(B, dtype=torch.float64, device=dev)
     lib = tb._lib
-    check(lib, lib.mz_select_actions(tb._h, _p(out.degrees), _p(visits), _p(actions), int(width), float(temperature),
-                                     int(bool(deterministic)), None if deterministic else _p(uniforms), _p(pos),
-                                     _p(act), _p(ent)), "select_actions")
+    with torch.cuda.device(dev):  # (a power table is uploaded to the current device)
+        check(lib, lib.mz_select_actions(tb._h, _p(out.degrees), _p(visits), _p(actions), int(width),
+                                         float(temperature), int(bool(deterministic)),
+                                         None if deterministic else _p(uniforms), _p(pos), _p(act), _p(ent)),
+              "select_actions")
     return pos, act, ent
 
 
@@ -122,10 +127,11 @@ def select_joint_actions(out: DeviceSearchOutput, temperature: float = 1.0, dete
     act = torch.empty(B, N, dtype=torch.int32, device=dev)
     ent = torch.empty(B, dtype=torch.float64, device=dev)
     lib = tb._lib
-    check(lib, lib.mz_select_actions_joint(tb._h, _p(out.degrees), _p(visits), _p(actions), int(width),
-                                           float(temperature), int(bool(deterministic)),
-                                           None if deterministic else _p(uniforms), _p(pos), _p(act), _p(ent)),
-          "select_joint_actions")
+    with torch.cuda.device(dev):
+        check(lib, lib.mz_select_actions_joint(tb._h, _p(out.degrees), _p(visits), _p(actions), int(width),
+                                               float(temperature), int(bool(deterministic)),
+                                               None if deterministic else _p(uniforms), _p(pos), _p(act), _p(ent)),
+              "select_joint_actions")
     return act, pos, ent
 
 

@@ -27,36 +27,64 @@ namespace {
 
 constexpr int kLanes = 64;
 
-// v ** e for a visit count v (core/utils.py:302): numpy evaluates it as the double power of
-// float64(v).  For an integer exponent the repeated product is exact, hence equal to libm pow,
-// whenever v**e < 2**53 (visit counts up to 9000 with e <= 4).
-__device__ __forceinline__ double visit_pow(int v, int ipow, double e) {
-    const double x = (double)v;
-    if (ipow <= 0) return pow(x, e);
-    double r = x;
-    for (int k = 1; k < ipow; ++k) r *= x;
-    return r;
+constexpr int kPowTableMax = MZ_SELECT_POW_TABLE_MAX;  // the host's table holds v ** e for v in 0..kPowTableMax
+
+// How v ** e is computed for a visit count v (core/utils.py:302: Python's float power of an int, the
+// host libm's pow).  ipow > 0: the repeated product x * x * .. (ipow factors) for v <= exact_max, the
+// largest v with v ** ipow <= 2**53: every partial product is then an integer below 2**53, so the
+// product is exact and equal to pow.  table: the host's own pow((double)v, e) for v in 0..kPowTableMax
+// (NULL: none), for every count the product does not cover.  A count that neither covers refuses its row.
+struct PowPlan {
+    int ipow, exact_max;
+    const double *table;
+};
+
+__device__ __forceinline__ bool pow_in_product(int v, const PowPlan &p) { return p.ipow > 0 && v <= p.exact_max; }
+
+__device__ __forceinline__ bool pow_covered(int v, const PowPlan &p) {
+    return pow_in_product(v, p) || (p.table && v >= 0 && v <= kPowTableMax);
+}
+
+// v ** e for a covered count (pow_covered)
+__device__ __forceinline__ double visit_pow(int v, const PowPlan &p) {
+    if (pow_in_product(v, p)) {
+        const double x = (double)v;
+        double r = x;
+        for (int k = 1; k < p.ipow; ++k) r *= x;
+        return r;
+    }
+    return p.table[v];
 }
 
 // select_action for root i (core/utils.py:289-316): the chosen child's position, written to pos_out
-// with the entropy; -1 for a root without children or visits.  The body of k_select_actions and of
-// k_select_actions_joint, which differ in the action columns they copy.
+// with the entropy; -1 (and a NaN entropy) for a root without children or visits, of a degree past the
+// row's width, or holding a count whose power is not covered (PowPlan).  The body of k_select_actions
+// and of k_select_actions_joint, which differ in the action columns they copy.
 __device__ __forceinline__ int select_position(int i, const int *__restrict__ deg, const int *__restrict__ visits,
-                                               int width, int ipow, double e, int deterministic,
+                                               int width, const PowPlan &pp, int deterministic,
                                                const double *__restrict__ uniforms, int *pos_out, double *ent_out) {
     const int n = deg[i];
     const int *row = visits + (long long)i * width;
     long long vsum = 0;
+    bool covered = true;
     if (n <= width)  // (a degree past the row's width is refused below, and never read)
-        for (int j = 0; j < n; ++j) vsum += row[j];
-    if (n <= 0 || n > width || vsum <= 0) {  // assert sum(visit_counts) > 0 (core/utils.py:301)
+        for (int j = 0; j < n; ++j) {
+            vsum += row[j];
+            covered = covered && pow_covered(row[j], pp);
+        }
+    if (n <= 0 || n > width || vsum <= 0 || !covered) {  // assert sum(visit_counts) > 0 (core/utils.py:301)
         pos_out[i] = -1;
         if (ent_out) ent_out[i] = NAN;
         return -1;
     }
     // total_count = sum(action_probs): Python's sum, left to right from 0 (utils.py:304)
     double total = 0.0;
-    for (int j = 0; j < n; ++j) total += visit_pow(row[j], ipow, e);
+    for (int j = 0; j < n; ++j) total += visit_pow(row[j], pp);
+    if (!(total < INFINITY)) {  // the powers overflow: numpy's choice refuses the NaN probabilities
+        pos_out[i] = -1;
+        if (ent_out) ent_out[i] = NAN;
+        return -1;
+    }
     int pos = 0;
     if (deterministic) {
         for (int j = 1; j < n; ++j)
@@ -65,12 +93,12 @@ __device__ __forceinline__ int select_position(int i, const int *__restrict__ de
         // np_random.choice(n, p=probs): cdf = probs.cumsum(); cdf /= cdf[-1];
         // cdf.searchsorted(u, side='right')
         double last = 0.0;
-        for (int j = 0; j < n; ++j) last += visit_pow(row[j], ipow, e) / total;
+        for (int j = 0; j < n; ++j) last += visit_pow(row[j], pp) / total;
         const double u = uniforms[i];
         double c = 0.0;
         pos = n - 1;
         for (int j = 0; j < n; ++j) {
-            c += visit_pow(row[j], ipow, e) / total;
+            c += visit_pow(row[j], pp) / total;
             if (c / last > u) {
                 pos = j;
                 break;
@@ -81,10 +109,10 @@ __device__ __forceinline__ int select_position(int i, const int *__restrict__ de
     if (ent_out) {
         // scipy.stats.entropy(action_probs, base=2): pk / sum(pk), sum of -pk log pk, / log(2)
         double ps = 0.0;
-        for (int j = 0; j < n; ++j) ps += visit_pow(row[j], ipow, e) / total;
+        for (int j = 0; j < n; ++j) ps += visit_pow(row[j], pp) / total;
         double h = 0.0;
         for (int j = 0; j < n; ++j) {
-            const double pk = (visit_pow(row[j], ipow, e) / total) / ps;
+            const double pk = (visit_pow(row[j], pp) / total) / ps;
             if (pk > 0.0) h -= pk * log(pk);
         }
         ent_out[i] = h / log(2.0);
@@ -94,13 +122,13 @@ __device__ __forceinline__ int select_position(int i, const int *__restrict__ de
 
 __global__ __launch_bounds__(kLanes) void k_select_actions(int B, int N, const int *__restrict__ deg,
                                                            const int *__restrict__ visits,
-                                                           const int *__restrict__ actions, int width, int ipow,
-                                                           double e, int deterministic,
+                                                           const int *__restrict__ actions, int width, PowPlan pp,
+                                                           int deterministic,
                                                            const double *__restrict__ uniforms, int *pos_out,
                                                            int *act_out, double *ent_out) {
     const int i = blockIdx.x * kLanes + threadIdx.x;
     if (i >= B) return;
-    const int pos = select_position(i, deg, visits, width, ipow, e, deterministic, uniforms, pos_out, ent_out);
+    const int pos = select_position(i, deg, visits, width, pp, deterministic, uniforms, pos_out, ent_out);
     // sampled_actions[pos, 0]
     act_out[i] = pos < 0 ? -1 : actions[(long long)i * width * N + (long long)pos * N];
 }
@@ -110,12 +138,12 @@ __global__ __launch_bounds__(kLanes) void k_select_actions(int B, int N, const i
 __global__ __launch_bounds__(kLanes) void k_select_actions_joint(int B, int N, const int *__restrict__ deg,
                                                                  const int *__restrict__ visits,
                                                                  const int *__restrict__ actions, int width,
-                                                                 int ipow, double e, int deterministic,
+                                                                 PowPlan pp, int deterministic,
                                                                  const double *__restrict__ uniforms, int *pos_out,
                                                                  int *act_out, double *ent_out) {
     const int i = blockIdx.x * kLanes + threadIdx.x;
     if (i >= B) return;
-    const int pos = select_position(i, deg, visits, width, ipow, e, deterministic, uniforms, pos_out, ent_out);
+    const int pos = select_position(i, deg, visits, width, pp, deterministic, uniforms, pos_out, ent_out);
     for (int k = 0; k < N; ++k)
         act_out[(long long)i * N + k] = pos < 0 ? -1 : actions[((long long)i * width + pos) * N + k];
 }
@@ -448,6 +476,83 @@ int device_plan(int n, hipStream_t stream, DevicePlan *out) {
     return MZ_OK;
 }
 
+// The host half of PowPlan for e = 1 / temperature: the product's exponent and domain, from e alone.
+// needs_table: some count in 0..kPowTableMax lies outside the product's domain.
+struct HostPowPlan {
+    double e;
+    int ipow, exact_max;
+    bool needs_table;
+};
+
+HostPowPlan host_pow_plan(double temperature) {
+    HostPowPlan p{1.0 / temperature, 0, -1, true};  // 1 / temperature, as Python computes it
+    if (p.e == floor(p.e) && p.e >= 1.0 && p.e <= 8.0) {
+        p.ipow = (int)p.e;
+        // the largest int32 v with v ** ipow <= 2**53, in exact integer arithmetic
+        const unsigned __int128 lim = (unsigned __int128)1 << 53;
+        long long lo = 1, hi = 0x7fffffffLL;
+        while (lo < hi) {
+            const long long mid = (lo + hi + 1) / 2;
+            unsigned __int128 r = 1;
+            for (int k = 0; k < p.ipow && r <= lim; ++k) r *= (unsigned __int128)mid;  // (r < 2**84: no overflow)
+            if (r <= lim) lo = mid;
+            else hi = mid - 1;
+        }
+        p.exact_max = (int)lo;
+        p.needs_table = p.exact_max < kPowTableMax;
+    }
+    return p;
+}
+
+// table[v] = v ** e as the reference's Python computes it: the host libm's pow of float(v)
+void fill_pow_table(double e, double *table, int len) {
+    for (int v = 0; v < len; ++v) table[v] = pow((double)v, e);
+}
+
+// The device copy of each exponent's table, built on first use and kept (as the pairwise plans).
+struct DevicePowTable {
+    int device;
+    double e;
+    double *buf;
+};
+std::mutex g_pow_lock;
+std::vector<DevicePowTable> g_pow_tables;
+constexpr size_t kMaxPowTables = 16;
+
+int device_pow_table(const std::string &name, double e, hipStream_t stream, const double **out) {
+    int device = 0;
+    if (hipGetDevice(&device) != hipSuccess) return mz_internal_fail(MZ_ERR_DEVICE, (name + ": no device").c_str());
+    std::lock_guard<std::mutex> guard(g_pow_lock);
+    for (const DevicePowTable &t : g_pow_tables)
+        if (t.device == device && t.e == e) {
+            *out = t.buf;
+            return MZ_OK;
+        }
+    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+    if (hipStreamIsCapturing(stream, &cap) != hipSuccess || cap != hipStreamCaptureStatusNone) {
+        (void)hipGetLastError();
+        return mz_internal_fail(MZ_ERR_RUNTIME,
+                                (name + ": first call for this temperature inside a stream capture (its power "
+                                        "table is uploaded on first use: call once before capturing)").c_str());
+    }
+    std::vector<double> host(kPowTableMax + 1);
+    fill_pow_table(e, host.data(), (int)host.size());
+    if (g_pow_tables.size() >= kMaxPowTables) {  // (hipFree waits for the device: no launch still reads it)
+        (void)hipFree(g_pow_tables.front().buf);
+        g_pow_tables.erase(g_pow_tables.begin());
+    }
+    DevicePowTable d{device, e, nullptr};
+    if (hipMalloc((void **)&d.buf, host.size() * sizeof(double)) != hipSuccess ||
+        hipMemcpy(d.buf, host.data(), host.size() * sizeof(double), hipMemcpyHostToDevice) != hipSuccess) {
+        if (d.buf) (void)hipFree(d.buf);
+        (void)hipGetLastError();
+        return mz_internal_fail(MZ_ERR_DEVICE, (name + ": power table upload failed").c_str());
+    }
+    g_pow_tables.push_back(d);
+    *out = d.buf;
+    return MZ_OK;
+}
+
 // mz_internal_launch_info with the handle's active roots for B: the consumers' buffers hold rows
 // [0, active) (include/mzdriver.h mz_set_active_roots)
 int consumer_info(mz_batch *b, int *B, int *A, hipStream_t *stream) {
@@ -490,11 +595,15 @@ static int select_actions(const char *fn, bool joint, mz_batch *b, const int32_t
         return mz_internal_fail(MZ_ERR_ARG, (name + ": null buffer").c_str());
     if (width < 1) return mz_internal_fail(MZ_ERR_ARG, (name + ": width must be >= 1").c_str());
     if (!(temperature > 0.0)) return mz_internal_fail(MZ_ERR_ARG, (name + ": temperature must be > 0").c_str());
-    const double e = 1.0 / temperature;  // 1 / temperature, as Python computes it
-    const int ipow = (e == floor(e) && e >= 1.0 && e <= 8.0) ? (int)e : 0;
+    const HostPowPlan hp = host_pow_plan(temperature);
+    PowPlan pp{hp.ipow, hp.exact_max, nullptr};
+    if (hp.needs_table) {
+        rc = device_pow_table(name, hp.e, stream, &pp.table);
+        if (rc) return rc;
+    }
     hipLaunchKernelGGL(joint ? k_select_actions_joint : k_select_actions, dim3((B + kLanes - 1) / kLanes),
                        dim3(kLanes), 0, stream, B, mz_internal_agent_num(b), (const int *)degrees,
-                       (const int *)visits, (const int *)actions, width, ipow, e, deterministic, uniforms,
+                       (const int *)visits, (const int *)actions, width, pp, deterministic, uniforms,
                        (int *)pos_out, (int *)action_out, entropy_out);
     mz_internal_enqueued(b);
     return launch_status();
@@ -512,6 +621,20 @@ int mz_select_actions_joint(mz_batch *b, const int32_t *degrees, const int32_t *
                             int32_t *pos_out, int32_t *action_out, double *entropy_out) {
     return select_actions("mz_select_actions_joint", true, b, degrees, visits, actions, width, temperature,
                           deterministic, uniforms, pos_out, action_out, entropy_out);
+}
+
+int mz_select_pow_plan(double temperature, int32_t *ipow, int32_t *exact_max, int32_t *uses_table, double *table,
+                       int table_len) {
+    if (!ipow || !exact_max || !uses_table) return mz_internal_fail(MZ_ERR_ARG, "mz_select_pow_plan: null argument");
+    if (!(temperature > 0.0)) return mz_internal_fail(MZ_ERR_ARG, "mz_select_pow_plan: temperature must be > 0");
+    if (table && (table_len < 0 || table_len > kPowTableMax + 1))
+        return mz_internal_fail(MZ_ERR_ARG, "mz_select_pow_plan: table_len outside 0..MZ_SELECT_POW_TABLE_MAX + 1");
+    const HostPowPlan hp = host_pow_plan(temperature);
+    *ipow = hp.ipow;
+    *exact_max = hp.exact_max;
+    *uses_table = hp.needs_table ? 1 : 0;
+    if (table) fill_pow_table(hp.e, table, table_len);
+    return MZ_OK;
 }
 
 int mz_eps_greedy(mz_batch *b, const int32_t *legal, int64_t legal_stride, float eps, const float *u_eps,

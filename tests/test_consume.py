@@ -23,36 +23,82 @@ import torch
 from consume import categorical_given, eps_greedy_given, reanalyze_policy, select_action, selfplay_step
 
 
-def kernel_select(row, temperature, deterministic, u):
-    """The arithmetic of k_select_actions (mzconsume.hip), in Python floats."""
+POW_TABLE_MAX = 65535  # MZ_SELECT_POW_TABLE_MAX (include/mzconsume.h)
+
+
+def kernel_pow_plan(temperature):
+    """host_pow_plan of mzconsume.hip (mz_select_pow_plan): (e, ipow, exact_max).  ipow is the exponent of
+    the in-kernel repeated product (0: none), used for counts up to exact_max, the largest int32 v with
+    v ** ipow <= 2**53 (Python's integers: exact)."""
     e = 1.0 / temperature
-    ipow = int(e) if (e == math.floor(e) and 1.0 <= e <= 8.0) else 0
+    if not (e == math.floor(e) and 1.0 <= e <= 8.0):
+        return e, 0, -1
+    ipow = int(e)
+    lo, hi = 1, 2 ** 31 - 1
+    while lo < hi:
+        mid = (lo + hi + 1) // 2
+        lo, hi = (mid, hi) if mid ** ipow <= 2 ** 53 else (lo, mid - 1)
+    return e, ipow, lo
 
-    def vp(v):
-        if ipow == 0:
-            return float(v) ** e
-        r = float(v)
-        for _ in range(ipow - 1):
-            r *= float(v)
-        return r
 
-    n = len(row)
-    total = 0.0
+def kernel_powers(row, temperature):
+    """visit_pow of mzconsume.hip over a row: the repeated product inside its domain, else the host's
+    table entry (libm's pow of float(v), which is Python's own float power; tests/test_consume_edges.py
+    pins the library's table against it).  None when a count is covered by neither: the row is refused."""
+    e, ipow, exact_max = kernel_pow_plan(temperature)
+    out = []
     for v in row:
-        total += vp(v)
+        v = int(v)
+        if ipow > 0 and v <= exact_max:
+            r = float(v)
+            for _ in range(ipow - 1):
+                r *= float(v)
+        elif 0 <= v <= POW_TABLE_MAX:
+            try:
+                r = float(v) ** e
+            except OverflowError:  # (libm's pow returns inf where Python raises)
+                r = math.inf
+        else:
+            return None
+        out.append(r)
+    return out
+
+
+def kernel_cdf(row, temperature):
+    """The values k_select_actions compares with the uniform, c / last for every child in order (Python
+    floats: the kernel's own sequence of sums and divisions); None for a refused row."""
+    p = kernel_powers(row, temperature)
+    if p is None:
+        return None
+    total = 0.0
+    for x in p:
+        total += x
+    if not total < math.inf:
+        return None
+    last = 0.0
+    for x in p:
+        last += x / total
+    out, c = [], 0.0
+    for x in p:
+        c += x / total
+        out.append(c / last)
+    return out
+
+
+def kernel_select(row, temperature, deterministic, u):
+    """The arithmetic of k_select_actions (mzconsume.hip), in Python floats; -1 for a refused row."""
+    cdf = kernel_cdf(row, temperature)
+    if cdf is None:
+        return -1
+    n = len(row)
     if deterministic:
         pos = 0
         for j in range(1, n):
             if row[j] > row[pos]:
                 pos = j
         return pos
-    last = 0.0
-    for v in row:
-        last += vp(v) / total
-    c = 0.0
-    for j, v in enumerate(row):
-        c += vp(v) / total
-        if c / last > u:
+    for j in range(n):
+        if cdf[j] > u:
             return j
     return n - 1
 
